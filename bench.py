@@ -3,9 +3,11 @@
 (B=8 per GPU, C=80, T=1024, L=256) — BASELINE.json configs[1] — on N MI355X GPUs of one node.
 
 A "step" is one complete sampler run (50 denoiser evaluations + 50 fused updates) over one
-batch per GPU.  One JSON line is printed by rank 0 (contract in the task description), with
-`roofline` (dominant kernel = the implicit-GEMM family, timed live with HIP events) and
-`cpu_baseline` (the oracle restatement timed on the host cores; bounded sample).
+batch per GPU.  One JSON line is printed by rank 0 (contract in the task description).  A plain
+run sets up, warms up, times `--steps` runs and prints the line; `--dump-outputs DIR` writes the
+mels of the last timed run beside it.  `--full` adds `roofline` (dominant kernel family, timed
+live with HIP events), the engine life-cycle costs, `cpu_baseline` (the oracle restatement timed
+on the host cores; bounded sample) with the UNet parity check, and the other configurations.
 """
 import argparse
 import json
@@ -111,6 +113,21 @@ PARITY_TOL = 1e-3         # BASELINE.json north_star: UNet output <= 1e-3 relati
 DRY_KW = dict(in_channels=24, out_channels=8, block_out_channels=(32, 64, 96, 128), norm_num_groups=8,
               cross_attention_dim=32, attention_head_dim=8, addition_embed_type="text",
               resnet_time_scale_shift="scale_shift", addition_embed_type_num_heads=8)
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much
+
+
+def dump_outputs(path, arrays):
+    """Write every array as path/<name>.npy in float32.  If they would exceed DUMP_MAX_BYTES together, each is cut to a fixed
+    strided sample of its flattened elements (the same elements on every run with the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    per = DUMP_MAX_BYTES // len(arrays) // 4          # elements per array
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > per:
+            a = a.reshape(-1)[::-(-a.size // per)]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def flops_model(B, T, L):
@@ -375,6 +392,11 @@ def main():
                     help="split the per-GPU batch into this many concurrent sub-batches (own engine + HIP stream each)")
     ap.add_argument("--keep-handover", action="store_true", default=os.environ.get("DVITS_BENCH_KEEP_HANDOVER") == "1",
                     help="with --streams k: the engines keep their in-launch hand-overs (plan each with DVITS_CU_BUDGET = CUs / k)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, engine life-cycle costs, CPU baseline with the "
+                         "UNet parity check, the other single-GPU BASELINE configurations (the --no-* flags below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed runs, write the mels of the last one as DIR/mel.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
@@ -384,6 +406,10 @@ def main():
     ap.add_argument("--dist-timeout", type=float, default=float(os.environ.get("DVITS_DIST_TIMEOUT_S", "180")),
                     help="seconds a rank waits in the rendezvous / a collective before it gives up")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:        # a plain run measures the headline only
+        args.no_roofline = args.no_cpu_baseline = args.no_other_configs = True
     dry = args.dry_run_cpu
     if dry:      # small enough for 8 ranks on a few CPU cores; explicit flags still win
         defaults = {"batch": 2, "frames": 24, "prompt": 10, "solver_steps": 4}
@@ -531,6 +557,8 @@ def main():
         if world > 1:
             torch.distributed.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mel": out.float().cpu().numpy()})     # [global batch, mel channels, frames]
 
     frames_per_s = G * T * args.steps / dt
     result = {

@@ -11,6 +11,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +48,29 @@ def test_dry_run_rank_path(world):
     # value = units ALL ranks processed / that time
     assert d["value"] == pytest.approx(world * 2 * 24 * 2 / (d["ms_per_step"] * 2e-3), rel=1e-6)
     assert "cpu_baseline" not in d and "roofline" not in d     # a rehearsal, not a measurement
+
+
+def test_dump_outputs_are_the_gathered_mels_and_repeat(tmp_path):
+    """--dump-outputs writes the last timed run's mels of the whole job (rank 0, after the all-gather) in float32, and the same
+    arguments give the same inputs: two runs write the same array."""
+    mels = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        p = subprocess.run([sys.executable, BENCH, "--dry-run-cpu", "--gpus", "2", "--steps", "1", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=_clean_env(), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert _last_json(p.stdout)["steps"] == 1
+        assert sorted(os.listdir(d)) == ["mel.npy"]
+        mels.append(np.load(d / "mel.npy"))
+    assert mels[0].dtype == np.float32 and mels[0].shape == (2 * 2, 8, 24)     # [global batch, mel channels, frames]
+    assert np.isfinite(mels[0]).all() and np.abs(mels[0]).max() > 0
+    assert np.array_equal(mels[0], mels[1])
+
+
+def test_steps_below_one_are_refused():
+    p = subprocess.run([sys.executable, BENCH, "--dry-run-cpu", "--steps", "0"], env=_clean_env(), capture_output=True,
+                       text=True, timeout=300)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
 
 
 def test_rank_failure_stops_the_job_quickly():

@@ -18,6 +18,19 @@ def test_flops_model_matches_the_survey_counts():
     assert abs(bench.flops_model(8, 1024, 256) / 1e9 - 316.1) < 0.5
 
 
+def test_dump_outputs_stays_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    a = np.arange(6 * 7 * 5, dtype=np.float64).reshape(6, 7, 5)
+    bench.dump_outputs(str(tmp_path / "full"), {"mel": a})
+    got = np.load(tmp_path / "full" / "mel.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a)            # small outputs are written whole
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 4 * 40)             # room for 40 float32 elements per array
+    bench.dump_outputs(str(tmp_path / "cut"), {"mel": a, "other": a[:1]})
+    got = np.load(tmp_path / "cut" / "mel.npy")
+    assert got.size <= 40 and np.array_equal(got, a.reshape(-1)[::6])  # a fixed strided sample of the flattened array
+    assert np.array_equal(np.load(tmp_path / "cut" / "other.npy"), a[:1])
+
+
 def test_pmc_figures_are_tied_to_the_build():
     from diff_vits_amd import _lib
     ver = _lib.lib().dv_version().decode()
