@@ -18,6 +18,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // ----------------------------------------------------------------------------- errors
@@ -408,6 +409,21 @@ struct Builder {
     }
     cur_kind = "misc"; cur_flops = 0; cur_desc.clear(); cur_gp = nullptr;
   }
+  // a launch that counts towards dv_unet_stats: `kind` and `desc` label it in the per-operation table (bench.py sums the
+  // FLOPs by kind, tools/profile_ops.py groups by desc)
+  void emit_launch(std::vector<OpFn>& ops, const char* kind, double flops, std::string desc, OpFn f, const PersistOp* pop = nullptr) {
+    cur_kind = kind; cur_flops = flops; cur_desc = std::move(desc);
+    if (!dry) u->flops += flops;
+    emit(ops, std::move(f), pop);
+  }
+  static std::string strf(const char* fmt, ...) {
+    char buf[128];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return buf;
+  }
   // descriptor of a GEMM for the persistent schedule, or false if its shape is outside what persist.hip instantiates
   bool persist_gemm(const GemmParams& gin, PersistOp& po) {
     if (prec != DV_PREC_BF16X3 || gin.epi == EPI_STORE_NCT || !gin.w_lo) return false;
@@ -571,17 +587,13 @@ struct Builder {
         launch_relayout_frag(w->lo, w->flo, w->N_pad, w->Kp, pack_stream) != hipSuccess) { err = "relayout launch failed"; return false; }
     return true;
   }
+  static double chain_flops(const ChainParams& cp) { return 2.0 * (double)cp.M * cp.C * cp.C * (1 + cp.passes); }
   // `extra_flops`: work of the launch beyond its two K = C contractions (the in-chain cross attention and its to_out GEMM) - part
   // of the operation's own count, so that the per-operation table and the family sums agree with dv_unet_stats
   void chain(std::vector<OpFn>& ops, const ChainParams& cp, const char* what, double extra_flops = 0.0) {
-    cur_kind = "chain";
-    cur_flops = 2.0 * (double)cp.M * cp.C * cp.C * (1 + cp.passes) + extra_flops;
-    char buf[96];
-    snprintf(buf, sizeof(buf), "%s M=%d C=%d N2=%d", what, cp.M, cp.C, cp.passes * cp.C);
-    cur_desc = buf;
-    if (!dry) u->flops += cur_flops;
     const int pr = prec;
-    emit(ops, [cp, pr](hipStream_t st) { return launch_chain2(cp, pr, st); });
+    emit_launch(ops, "chain", chain_flops(cp) + extra_flops, strf("%s M=%d C=%d N2=%d", what, cp.M, cp.C, cp.passes * cp.C),
+                [cp, pr](hipStream_t st) { return launch_chain2(cp, pr, st); });
   }
   // GroupNorm (+ temb scale/shift) (+ SiLU) of a GEMM's own output finished in ITS epilogue (gemm_tile.h GNX; DVITS_GNX=0
   // restores the k_gn_apply launch): fills g.gnx and allocates the normalised planes; false if launch_gemm would refuse.
@@ -601,9 +613,20 @@ struct Builder {
   // `skip`: the consumer normalises [g's output | skip] (an up-path resnet block's norm1); the skip's share of the planes goes
   // to *sk_y (and *sk_raw, if the consumer's shortcut wants the raw tensor as planes).  DVITS_GNX_CONCAT=0: not planned.
   bool gnx_cat_on = [] { const char* e = getenv("DVITS_GNX_CONCAT"); return !(e && e[0] == '0'); }();
+  // what every in-launch hand-over needs: all workgroups of the launch co-resident, nothing else on the device beside them
+  bool handover_ok() const { return gnx_on && u->exclusive && !arena.exact && n_cu > 0; }
+  // `n` exchange words of the pool for one launch's in-launch hand-over (the caller has checked that they fit)
+  struct Handover { unsigned long long* flags; unsigned* status; };
+  Handover handover(size_t n) {
+    Handover h{dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used,
+               dry ? reinterpret_cast<unsigned*>(0x1000) : u->gnx_status};
+    gnx_used += (n + 1) & ~(size_t)1;
+    if (!dry) { u->gnx_words = gnx_used; u->gnx_ops++; }
+    return h;
+  }
   bool gnx_setup(GemmParams& g, const std::string& pre, float eps, const float* tscale, const float* tshift, int ld_t, bool silu,
                  Planes* y, const Act* skip = nullptr, Planes* sk_y = nullptr, Planes* sk_raw = nullptr) {
-    if (!gnx_on || !u->exclusive || arena.exact || autotune_on() || !g.stats16 || n_cu <= 0) return false;
+    if (!handover_ok() || autotune_on() || !g.stats16) return false;
     if (skip && (!gnx_cat_on || !skip->p || !skip->stat16 || skip->Tp != g.T_out || tscale)) return false;
     GemmParams t = g;
     t.B = B;
@@ -630,10 +653,8 @@ struct Builder {
     gx.gamma = W(pre + ".weight"); gx.beta = W(pre + ".bias"); gx.eps = eps;
     gx.tscale = tscale; gx.tshift = tshift; gx.ld_t = ld_t; gx.silu = silu ? 1 : 0;
     gx.spin_max = gnx_spin;
-    gx.xchg = dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used;
-    gx.status = dry ? reinterpret_cast<unsigned*>(0x1000) : u->gnx_status;
-    gnx_used += ((size_t)nw + 1) & ~(size_t)1;
-    if (!dry) u->gnx_words = gnx_used;
+    const Handover h = handover((size_t)nw);
+    gx.xchg = h.flags; gx.status = h.status;
     *y = alloc_planes((size_t)M * N);
     gx.y_hi = y->hi; gx.y_lo = y->lo;
     if (skip) {
@@ -642,7 +663,6 @@ struct Builder {
       gx.sk_y_hi = sk_y->hi; gx.sk_y_lo = sk_y->lo;
       if (sk_raw) { *sk_raw = alloc_planes((size_t)M * skip->C); gx.sk_raw_hi = sk_raw->hi; gx.sk_raw_lo = sk_raw->lo; }
     }
-    if (!dry) u->gnx_ops++;
   }
 
   // The build loop announces the single GroupNorm consumer of the next producer's output (a resnet block's norm1, or
@@ -660,71 +680,50 @@ struct Builder {
     announce_norm(tp + "norm", false);
     next_norm.eps = 1e-6f; next_norm.silu = false;
   }
-  void offer_next(GemmParams& g, Act& out) {
+  // The producer's share of the offer: plans the in-launch GroupNorm of its output and allocates the normalised planes it
+  // will write (y; the skip's shares sy, sr), or returns false.  The producer is a GEMM ...
+  bool gnx_offer(GemmParams& g, const NextNorm& nn, Planes* y, Planes* sy, Planes* sr) {
+    return gnx_setup(g, nn.pre, nn.eps, nullptr, nullptr, 0, nn.silu, y, nn.skip.C > 0 ? &nn.skip : nullptr, sy, nn.raw ? sr : nullptr);
+  }
+  // ... or a feed-forward launch: the C = 128 chain (k_chain_ff: one workgroup per row block), or the split launch of the
+  // C = 256 / 384 blocks (k_ff_split: its finishing tiles are [64 rows x C / nspl columns], all resident)
+  static int ff_gnx_plan(const ChainFFParams& fp, int n_cu) { return chain_ff_gnx_plan(fp, n_cu); }
+  static int ff_gnx_plan(const FFSplitParams& fp, int n_cu) { return ff_split_gnx_plan(fp, n_cu); }
+  template <class FF> bool gnx_offer(FF& fp, const NextNorm& nn, Planes* y, Planes* sy, Planes* sr) {
+    const bool cat = nn.skip.C > 0;
+    if (!handover_ok() || !gnx_ff_on || !fp.stats16) return false;
+    if (cat && (!gnx_cat_on || !nn.skip.p || !nn.skip.stat16 || nn.skip.Tp != fp.T)) return false;
+    fp.gnx = GnxParams{};
+    fp.gnx.groups = u->cfg.norm_num_groups;
+    fp.gnx.sk_c = cat ? nn.skip.C : 0;
+    const int nw = ff_gnx_plan(fp, n_cu);
+    if (nw <= 0 || gnx_used + (size_t)nw > dv_unet::GNX_POOL) { fp.gnx = GnxParams{}; return false; }
+    gnx_fill(fp.gnx, nw, fp.M, fp.C, nn.pre, nn.eps, nullptr, nullptr, 0, nn.silu, y, cat ? &nn.skip : nullptr, sy, nn.raw ? sr : nullptr);
+    return true;
+  }
+  template <class P> void offer_next(P& prod, Act& out) {
     if (!next_norm.set) return;
     const NextNorm nn = next_norm;
     next_norm.set = false;
     Planes y, sy, sr;
+    if (!gnx_offer(prod, nn, &y, &sy, &sr)) return;
     const bool cat = nn.skip.C > 0;
-    if (!gnx_setup(g, nn.pre, nn.eps, nullptr, nullptr, 0, nn.silu, &y, cat ? &nn.skip : nullptr, &sy, nn.raw ? &sr : nullptr)) return;
     out.n_hi = y.hi; out.n_lo = y.lo; out.n_pre = nn.pre;
     if (cat) { out.sn_hi = sy.hi; out.sn_lo = sy.lo; out.sr_hi = sr.hi; out.sr_lo = sr.lo; }
     // (an up-path tensor has this one consumer, which reads it through the planes alone when its shortcut is a convolution)
     const bool fp32_unread = cat && nn.raw && !u->keep_intermediates;
-    if (nn.raw && !g.out_hi) {   // the consumer's folded 1x1 shortcut reads the raw tensor as split planes
-      Planes pl = alloc_planes((size_t)g.M * g.N);
-      out.pl_hi = pl.hi; out.pl_lo = pl.lo; g.out_hi = pl.hi; g.out_lo = pl.lo;
-    }
-    if (fp32_unread && cat_drop_fp32) g.out = nullptr;
+    if (nn.raw && !prod.out_hi) out_planes(prod, out);   // the consumer's folded 1x1 shortcut reads the raw tensor as split planes
+    if (fp32_unread && cat_drop_fp32) prod.out = nullptr;
   }
-  // ... when the producer is the C = 128 feed-forward chain (k_chain_ff: one workgroup per row block)
-  void offer_next(ChainFFParams& fp, Act& out) {
-    if (!next_norm.set) return;
-    const NextNorm nn = next_norm;
-    next_norm.set = false;
-    const bool cat = nn.skip.C > 0;
-    if (!gnx_on || !gnx_ff_on || !u->exclusive || arena.exact || !fp.stats16 || n_cu <= 0) return;
-    if (cat && (!gnx_cat_on || !nn.skip.p || !nn.skip.stat16 || nn.skip.Tp != fp.T)) return;
-    fp.gnx = GnxParams{};
-    fp.gnx.groups = u->cfg.norm_num_groups;
-    fp.gnx.sk_c = cat ? nn.skip.C : 0;
-    const int nw = chain_ff_gnx_plan(fp, n_cu);
-    if (nw <= 0 || gnx_used + (size_t)nw > dv_unet::GNX_POOL) { fp.gnx = GnxParams{}; return; }
-    Planes y, sy, sr;
-    gnx_fill(fp.gnx, nw, fp.M, fp.C, nn.pre, nn.eps, nullptr, nullptr, 0, nn.silu, &y, cat ? &nn.skip : nullptr, &sy, nn.raw ? &sr : nullptr);
-    out.n_hi = y.hi; out.n_lo = y.lo; out.n_pre = nn.pre;
-    if (cat) { out.sn_hi = sy.hi; out.sn_lo = sy.lo; out.sr_hi = sr.hi; out.sr_lo = sr.lo; }
-    if (nn.raw && !fp.out_hi) {
-      Planes pl = alloc_planes((size_t)fp.M * fp.C);
-      out.pl_hi = pl.hi; out.pl_lo = pl.lo; fp.out_hi = pl.hi; fp.out_lo = pl.lo;
-    }
-    if (cat && nn.raw && !u->keep_intermediates && cat_drop_fp32) fp.out = nullptr;
-  }
-  // ... when the producer is the split feed-forward launch of the C = 256 / 384 blocks (k_ff_split: its finishing tiles are
-  // [64 rows x C / nspl columns], all resident)
-  void offer_next(FFSplitParams& fp, Act& out) {
-    if (!next_norm.set) return;
-    const NextNorm nn = next_norm;
-    next_norm.set = false;
-    const bool cat = nn.skip.C > 0;
-    if (!gnx_on || !gnx_ff_on || !u->exclusive || arena.exact || !fp.stats16 || n_cu <= 0) return;
-    if (cat && (!gnx_cat_on || !nn.skip.p || !nn.skip.stat16 || nn.skip.Tp != fp.T)) return;
-    fp.gnx = GnxParams{};
-    fp.gnx.groups = u->cfg.norm_num_groups;
-    fp.gnx.sk_c = cat ? nn.skip.C : 0;
-    const int nw = ff_split_gnx_plan(fp, n_cu);
-    if (nw <= 0 || gnx_used + (size_t)nw > dv_unet::GNX_POOL) { fp.gnx = GnxParams{}; return; }
-    Planes y, sy, sr;
-    gnx_fill(fp.gnx, nw, fp.M, fp.C, nn.pre, nn.eps, nullptr, nullptr, 0, nn.silu, &y, cat ? &nn.skip : nullptr, &sy, nn.raw ? &sr : nullptr);
-    out.n_hi = y.hi; out.n_lo = y.lo; out.n_pre = nn.pre;
-    if (cat) { out.sn_hi = sy.hi; out.sn_lo = sy.lo; out.sr_hi = sr.hi; out.sr_lo = sr.lo; }
-    if (nn.raw && !fp.out_hi) {
-      Planes pl = alloc_planes((size_t)fp.M * fp.C);
-      out.pl_hi = pl.hi; out.pl_lo = pl.lo; fp.out_hi = pl.hi; fp.out_lo = pl.lo;
-    }
-    if (cat && nn.raw && !u->keep_intermediates && cat_drop_fp32) fp.out = nullptr;
+  // split planes of a producer's output [prod.M, out.C] beside its fp32 tensor (a resampling conv or a folded 1x1 shortcut reads them)
+  template <class P> void out_planes(P& prod, Act& out) {
+    Planes pl = alloc_planes((size_t)prod.M * out.C);
+    out.pl_hi = pl.hi; out.pl_lo = pl.lo; prod.out_hi = pl.hi; prod.out_lo = pl.lo;
   }
   bool ff_split_on = [] { const char* e = getenv("DVITS_FF_SPLIT"); return !(e && e[0] == '0'); }();
+  bool chain_ff_on = [] { const char* e = getenv("DVITS_CHAIN_FF"); return !(e && e[0] == '0'); }();
+  bool chain_split_on = [] { const char* e = getenv("DVITS_CHAIN_SPLIT"); return !(e && e[0] == '0'); }();
+  bool chain_xsplit_on = [] { const char* e = getenv("DVITS_CHAIN_XSPLIT"); return !(e && e[0] == '0'); }();
   bool qkv_split_on = [] { const char* e = getenv("DVITS_QKV_SPLIT"); return !(e && e[0] == '0'); }();
   int qkv_split_min_wg = [] { const char* e = getenv("DVITS_QKV_SPLIT_MIN_WG"); return e ? atoi(e) : 96; }();
   // (at C = 128 a workgroup of the 32-row chain streams 0.26 MB of weights: nothing to save - 18.1 us against 19.3 us on the split launch)
@@ -979,10 +978,7 @@ struct Builder {
       GemmParams g = gp_base(Tn, M, cout);
       if (!shortcut) { g.epi = EPI_RESIDUAL; g.res = x0.p; g.ldres = cout; }
       g.out = out.p; stat_out(g, out);
-      if (want_planes) {   // the next op is a resampling conv: hand it split planes instead of a k_split launch
-        Planes pl = alloc_planes((size_t)M * cout);
-        out.pl_hi = pl.hi; out.pl_lo = pl.lo; g.out_hi = pl.hi; g.out_lo = pl.lo;
-      }
+      if (want_planes) out_planes(g, out);   // the next op is a resampling conv: hand it split planes instead of a k_split launch
       const bool offered = next_norm.set;
       {
         Planes n2 = gnx1 ? n2x : norm_apply(ops, h, Act{}, p + "norm2", eps, tproj + toff, tproj + toff + cout, tproj_total, true, nullptr);
@@ -1024,16 +1020,10 @@ struct Builder {
     a.B = B; a.H = u->cfg.num_heads; a.Tq = Tq; a.Tk = Tk; a.d = C / u->cfg.num_heads;
     a.scale = 1.0f / sqrtf((float)a.d);
     a.nsplit = prec == DV_PREC_BF16X3 ? 3 : 1;
-    cur_kind = "attn"; cur_flops = 4.0 * B * a.H * (double)Tq * Tk * a.d;
-    {
-      char buf[96];
-      snprintf(buf, sizeof(buf), "Tq=%d Tk=%d d=%d H=%d", Tq, Tk, a.d, a.H);
-      cur_desc = buf;
-    }
-    if (!dry) u->flops += cur_flops;
     PersistOp po{};
     po.type = POP_ATTN; po.cfg = (a.d + 15) / 16 * 16; po.a = a;
-    emit(ops, [a](hipStream_t st) { return launch_attention(a, st); }, (prec == DV_PREC_BF16X3 && a.d % 4 == 0 && a.d <= 64) ? &po : nullptr);
+    emit_launch(ops, "attn", 4.0 * B * a.H * (double)Tq * Tk * a.d, strf("Tq=%d Tk=%d d=%d H=%d", Tq, Tk, a.d, a.H),
+                [a](hipStream_t st) { return launch_attention(a, st); }, (prec == DV_PREC_BF16X3 && a.d % 4 == 0 && a.d <= 64) ? &po : nullptr);
     return o;
   }
 
@@ -1045,14 +1035,8 @@ struct Builder {
     a.B = B; a.H = u->cfg.num_heads; a.Tq = Tq; a.Tk = Tk; a.d = C / u->cfg.num_heads;
     a.scale = 1.0f / sqrtf((float)a.d);
     a.nsplit = prec == DV_PREC_BF16X3 ? 3 : 1;
-    cur_kind = "attn"; cur_flops = 4.0 * B * a.H * (double)Tq * Tk * a.d;
-    {
-      char buf[96];
-      snprintf(buf, sizeof(buf), "Tq=%d Tk=%d d=%d H=%d frag", Tq, Tk, a.d, a.H);
-      cur_desc = buf;
-    }
-    if (!dry) u->flops += cur_flops;
-    emit(ops, [a](hipStream_t st) { return launch_attention_frag(a, st); });
+    emit_launch(ops, "attn", 4.0 * B * a.H * (double)Tq * Tk * a.d, strf("Tq=%d Tk=%d d=%d H=%d frag", Tq, Tk, a.d, a.H),
+                [a](hipStream_t st) { return launch_attention_frag(a, st); });
     return o;
   }
   bool attn_frag_on = [] { const char* e = getenv("DVITS_ATTN_FRAG"); return !(e && e[0] == '0'); }();
@@ -1069,273 +1053,254 @@ struct Builder {
     return attention_frag(ops, a, Tn, L, C);
   }
 
+  // LayerNorm of a sub-layer whose consumer is a k = 1 GEMM over [M, C] rows.  Two ways to feed it: (default) the producer GEMM
+  // also emits raw planes + per-row partial statistics and the consumer finishes the normalisation in its epilogue, 48 launches
+  // fewer per forward; (DVITS_FUSE_LN=0) k_ln_apply writes normalised split planes for the consumer GEMM.  With the transposed
+  // accumulator the row partials are in-lane sums and the fused schedule measures 4.27 vs 4.34 ms per forward.
+  struct LnIn { Planes pl; float* stat = nullptr; };
+  LnIn ln_planes(int M, int C) {   // the raw planes and row partials a producer writes
+    LnIn in;
+    in.pl = alloc_planes((size_t)M * C);
+    in.stat = alloc((size_t)M * (C / 32) * 2);
+    return in;
+  }
+  LnIn ln_produce(GemmParams& g, int M, int C) {   // producer side (fused mode only)
+    if (!fuse_ln) return LnIn{};
+    LnIn in = ln_planes(M, C);
+    g.out_hi = in.pl.hi; g.out_lo = in.pl.lo; g.rowstat_out = in.stat;
+    return in;
+  }
+  void ln_consume(std::vector<OpFn>& ops, GemmParams& g, LnIn& in, const float* x32, const PackedW* w, int M, int C) {
+    if (!fuse_ln) in.pl = ln_apply(ops, x32, M, C);
+    else { g.ln_stat = in.stat; g.ln_nblk = C / 32; g.ln_u = w->u; g.ln_eps = 1e-5f; }
+    g.seg[0] = seg(in.pl, C, Planes{}, 0, 1, 0);
+  }
+  void ln_release(LnIn& in) { release(in.pl); if (in.stat) release(in.stat); }
+
+  // One k_qkv_split launch (kernels_qkv.hip: 64-row blocks, the output columns of the chain's contractions split over C / 64
+  // workgroups, hand-overs through exchange words inside the launch).  The caller has checked its own conditions and that the
+  // words fit; false (nothing planned) if the kernel does not take `cp`.
+  bool qkv_split(std::vector<OpFn>& ops, ChainParams cp, std::string desc, double extra_flops = 0.0) {
+    if (!qkv_split_supported(cp, prec)) return false;
+    const Handover h = handover((size_t)qkv_split_flags(cp));
+    cp.nsplit = 1; cp.qs_flags = h.flags; cp.qs_status = h.status; cp.qs_spin = gnx_spin;
+    const int pr = prec;
+    emit_launch(ops, "chain", chain_flops(cp) + extra_flops, std::move(desc), [cp, pr](hipStream_t st) { return launch_qkv_split(cp, pr, st); });
+    return true;
+  }
+
+  // A Transformer2DModel block being planned: its shape and packed weights (w_ff and w_out are w_gg when ff.net.2 and proj_out
+  // are merged: merged_ffproj)
+  struct Xf {
+    std::string p, tb;
+    Act x;
+    int C, Tn, Tp, M;
+    const PackedW *w_in, *w_qkv, *w_o1, *w_q2, *w_o2, *w_gg, *w_ff, *w_out;
+    bool merged_ffproj;
+  };
+
   // Transformer2DModel + BasicTransformerBlock (reference transformer_1d.py:191-326, attention.py:130-203)
   Act transformer(std::vector<OpFn>& ops, const std::string& p, Act x, bool want_planes = false) {
-    const int C = x.C, Tn = x.T, Tp = x.Tp, M = B * Tp, D = u->cfg.cross_attention_dim;
+    const int C = x.C;
     const std::string tb = p + "transformer_blocks.0.";
-    const PackedW* w_in = pack(p + "proj_in", C, C, {{p + "proj_in.weight", 1, C, 1, C, 0, 0, "", 0}},
-                               {{p + "proj_in.bias", "", "", "", C, 0, 0, 0}});
-    const PackedW* w_qkv = pack(tb + "qkv1", 3 * C, C,
-                                {{tb + "attn1.to_q.weight", 0, C, 1, C, 0, 0, tb + "norm1.weight", 0},
-                                 {tb + "attn1.to_k.weight", 0, C, 1, C, 0, C, tb + "norm1.weight", 0},
-                                 {tb + "attn1.to_v.weight", 0, C, 1, C, 0, 2 * C, tb + "norm1.weight", 0}},
-                                {{"", "", tb + "attn1.to_q.weight", tb + "norm1.bias", C, C, 0, 0},
-                                 {"", "", tb + "attn1.to_k.weight", tb + "norm1.bias", C, C, C, 0},
-                                 {"", "", tb + "attn1.to_v.weight", tb + "norm1.bias", C, C, 2 * C, 0}});
-    const PackedW* w_o1 = pack(tb + "out1", C, C, {{tb + "attn1.to_out.0.weight", 0, C, 1, C, 0, 0, "", 0}},
-                               {{tb + "attn1.to_out.0.bias", "", "", "", C, 0, 0, 0}});
-    const PackedW* w_q2 = pack(tb + "q2", C, C, {{tb + "attn2.to_q.weight", 0, C, 1, C, 0, 0, tb + "norm2.weight", 0}},
-                               {{"", "", tb + "attn2.to_q.weight", tb + "norm2.bias", C, C, 0, 0}});
-    const PackedW* w_o2 = pack(tb + "out2", C, C, {{tb + "attn2.to_out.0.weight", 0, C, 1, C, 0, 0, "", 0}},
-                               {{tb + "attn2.to_out.0.bias", "", "", "", C, 0, 0, 0}});
-    const PackedW* w_gg = pack(tb + "geglu", 8 * C, C, {{tb + "ff.net.0.proj.weight", 0, C, 1, C, 0, 0, tb + "norm3.weight", 1}},
-                               {{tb + "ff.net.0.proj.bias", "", tb + "ff.net.0.proj.weight", tb + "norm3.bias", 8 * C, C, 0, 1}});
-    const bool merged_ffproj = merge_ff && fuse_ln && !u->keep_intermediates;
-    const PackedW* w_ff = merged_ffproj ? w_gg : pack(tb + "ffout", C, 4 * C, {{tb + "ff.net.2.weight", 0, 4 * C, 1, 4 * C, 0, 0, "", 0}},
-                               {{tb + "ff.net.2.bias", "", "", "", C, 0, 0, 0}});
-    const PackedW* w_out = merged_ffproj ? w_gg : pack(p + "proj_out", C, C, {{p + "proj_out.weight", 1, C, 1, C, 0, 0, "", 0}},
-                                {{p + "proj_out.bias", "", "", "", C, 0, 0, 0}});
-    if (!w_in || !w_qkv || !w_o1 || !w_q2 || !w_o2 || !w_gg || !w_ff || !w_out) return Act{};
-    (void)D;
+    Xf b{p, tb, x, C, x.T, x.Tp, B * x.Tp};
+    b.w_in = pack(p + "proj_in", C, C, {{p + "proj_in.weight", 1, C, 1, C, 0, 0, "", 0}},
+                  {{p + "proj_in.bias", "", "", "", C, 0, 0, 0}});
+    b.w_qkv = pack(tb + "qkv1", 3 * C, C,
+                   {{tb + "attn1.to_q.weight", 0, C, 1, C, 0, 0, tb + "norm1.weight", 0},
+                    {tb + "attn1.to_k.weight", 0, C, 1, C, 0, C, tb + "norm1.weight", 0},
+                    {tb + "attn1.to_v.weight", 0, C, 1, C, 0, 2 * C, tb + "norm1.weight", 0}},
+                   {{"", "", tb + "attn1.to_q.weight", tb + "norm1.bias", C, C, 0, 0},
+                    {"", "", tb + "attn1.to_k.weight", tb + "norm1.bias", C, C, C, 0},
+                    {"", "", tb + "attn1.to_v.weight", tb + "norm1.bias", C, C, 2 * C, 0}});
+    b.w_o1 = pack(tb + "out1", C, C, {{tb + "attn1.to_out.0.weight", 0, C, 1, C, 0, 0, "", 0}},
+                  {{tb + "attn1.to_out.0.bias", "", "", "", C, 0, 0, 0}});
+    b.w_q2 = pack(tb + "q2", C, C, {{tb + "attn2.to_q.weight", 0, C, 1, C, 0, 0, tb + "norm2.weight", 0}},
+                  {{"", "", tb + "attn2.to_q.weight", tb + "norm2.bias", C, C, 0, 0}});
+    b.w_o2 = pack(tb + "out2", C, C, {{tb + "attn2.to_out.0.weight", 0, C, 1, C, 0, 0, "", 0}},
+                  {{tb + "attn2.to_out.0.bias", "", "", "", C, 0, 0, 0}});
+    b.w_gg = pack(tb + "geglu", 8 * C, C, {{tb + "ff.net.0.proj.weight", 0, C, 1, C, 0, 0, tb + "norm3.weight", 1}},
+                  {{tb + "ff.net.0.proj.bias", "", tb + "ff.net.0.proj.weight", tb + "norm3.bias", 8 * C, C, 0, 1}});
+    b.merged_ffproj = merge_ff && fuse_ln && !u->keep_intermediates;
+    b.w_ff = b.merged_ffproj ? b.w_gg : pack(tb + "ffout", C, 4 * C, {{tb + "ff.net.2.weight", 0, 4 * C, 1, 4 * C, 0, 0, "", 0}},
+                                             {{tb + "ff.net.2.bias", "", "", "", C, 0, 0, 0}});
+    b.w_out = b.merged_ffproj ? b.w_gg : pack(p + "proj_out", C, C, {{p + "proj_out.weight", 1, C, 1, C, 0, 0, "", 0}},
+                                              {{p + "proj_out.bias", "", "", "", C, 0, 0, 0}});
+    if (!b.w_in || !b.w_qkv || !b.w_o1 || !b.w_q2 || !b.w_o2 || !b.w_gg || !b.w_ff || !b.w_out) return Act{};
 
-    // Two ways to feed the three LayerNorms: (default) the producer GEMM also emits raw planes + per-row partial
-    // statistics and the consumer finishes the normalisation in its epilogue, 48 launches fewer per forward;
-    // (DVITS_FUSE_LN=0) k_ln_apply writes normalised split planes for the consumer GEMM.  With the transposed
-    // accumulator the row partials are in-lane sums and the fused schedule measures 4.27 vs 4.34 ms per forward.
-    const int nblk = C / 32;
-    struct LnIn { Planes pl; float* stat = nullptr; };
-    auto ln_produce = [&](GemmParams& g) {   // producer side (fused mode only)
-      LnIn in;
-      if (!fuse_ln) return in;
-      in.pl = alloc_planes((size_t)M * C);
-      in.stat = alloc((size_t)M * nblk * 2);
-      g.out_hi = in.pl.hi; g.out_lo = in.pl.lo; g.rowstat_out = in.stat;
-      return in;
-    };
-    auto ln_consume = [&](GemmParams& g, LnIn& in, const float* x32, const PackedW* w) {
-      if (!fuse_ln) in.pl = ln_apply(ops, x32, M, C);
-      else { g.ln_stat = in.stat; g.ln_nblk = nblk; g.ln_u = w->u; g.ln_eps = 1e-5f; }
-      g.seg[0] = seg(in.pl, C, Planes{}, 0, 1, 0);
-    };
-    auto ln_release = [&](LnIn& in) { release(in.pl); if (in.stat) release(in.stat); };
-
-    const bool chained = chain_ok(Tp, C) && x.stat16;
     float* h3 = nullptr;
     LnIn l3;
-    if (chained && !(frag(w_in) && frag(w_qkv) && frag(w_o1) && frag(w_q2))) return Act{};
-    if (chained) {
-      // chain 1: GN(eps 1e-6) -> proj_in -> LN1 -> to_q | to_k | to_v   (3 launches -> 1)
-      float* h = alloc((size_t)M * C);
-      // K and V leave the chain as MFMA fragments of 32-key tiles (k_attention_frag multiplies them as they are):
-      // DVITS_ATTN_FRAG=0 restores fp32 q | k | v and the converting attention kernel
-      const int dh = C / u->cfg.num_heads;
-      const bool sa_frag = attn_frag_on && !arena.exact && C % u->cfg.num_heads == 0 && dh % 16 == 0 && dh <= 64;
-      float* qkv = alloc((size_t)M * (sa_frag ? 1 : 3) * C);
-      Planes kf, vf;
-      if (sa_frag) { kf = alloc_planes((size_t)M * C); vf = alloc_planes((size_t)M * C); }
-      {
-        ChainParams cp{};
-        cp.M = M; cp.C = C; cp.T = Tp; cp.Tv = Tn; cp.amode = 1;
-        cp.x = x.p; cp.stat16 = x.stat16; cp.gamma = W(p + "norm.weight"); cp.beta = W(p + "norm.bias"); cp.gn_eps = 1e-6f;
-        cp.groups = u->cfg.norm_num_groups;
-        cp.w1_hi = w_in->fhi; cp.w1_lo = w_in->flo; cp.Kp1 = w_in->Kp; cp.b1 = w_in->bias; cp.res = nullptr; cp.out1 = h;
-        cp.w2_hi = w_qkv->fhi; cp.w2_lo = w_qkv->flo; cp.Kp2 = w_qkv->Kp; cp.b2 = w_qkv->bias; cp.u2 = w_qkv->u;
-        cp.passes = 3; cp.out2 = qkv; cp.ldo2 = sa_frag ? C : 3 * C; cp.ln_eps = 1e-5f;
-        if (sa_frag) { cp.sa_kf_hi = kf.hi; cp.sa_kf_lo = kf.lo; cp.sa_vf_hi = vf.hi; cp.sa_vf_lo = vf.lo; }
-        {   // few row blocks: share the three passes out (DVITS_CHAIN_SPLIT=0: one workgroup per row block)
-          const char* es = getenv("DVITS_CHAIN_SPLIT");
-          const bool off = es && es[0] == '0';
-          const int rbs = M / 32, cus = n_cu > 0 ? n_cu : 256;
-          cp.nsplit = off ? 1 : (rbs * 3 <= cus ? 3 : (rbs * 2 <= cus ? 2 : 1));
-        }
-        // 64-row blocks with the output columns of both contractions split over C / 64 workgroups per row block (k_qkv_split,
-        // kernels_qkv.hip: an all-gather of h inside the launch - planned like k_ff_split's hand-over; DVITS_QKV_SPLIT=0: the
-        // 32-row chain above) wherever that gives the launch at least qkv_split_min_wg workgroups
-        const int n_qflags = qkv_split_flags(cp);
-        if (qkv_split_on && C >= qkv_split_min_c && sa_frag && gnx_on && u->exclusive && !arena.exact && !autotune_on() && n_cu > 0 && qkv_split_supported(cp, prec) &&
-            n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL) {   // (one round of workgroups: at B = 16 - 384 / 512 of them - the 32-row chain is the faster one, 4.09 vs 4.19 ms per forward)
-          cp.nsplit = 1;
-          cp.qs_flags = dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used;
-          cp.qs_status = dry ? reinterpret_cast<unsigned*>(0x1000) : u->gnx_status;
-          cp.qs_spin = gnx_spin;
-          gnx_used += ((size_t)n_qflags + 1) & ~(size_t)1;
-          if (!dry) { u->gnx_words = gnx_used; u->gnx_ops++; }
-          cur_kind = "chain";
-          cur_flops = 2.0 * (double)cp.M * cp.C * cp.C * 4.0;
-          char buf[96];
-          snprintf(buf, sizeof(buf), "norm+proj_in+LN+q|Kfrag|Vfrag (%d wg / 64 rows) M=%d C=%d N2=%d", C / 64, cp.M, cp.C, 3 * cp.C);
-          cur_desc = buf;
-          if (!dry) u->flops += cur_flops;
-          const int pr = prec;
-          emit(ops, [cp, pr](hipStream_t st) { return launch_qkv_split(cp, pr, st); });
-        } else
-        chain(ops, cp, sa_frag ? "norm+proj_in+LN+q|Kfrag|Vfrag" : "norm+proj_in+LN+qkv");
-      }
-      probe(p + "proj_in", h, Tn, C);
-      Planes ao;
-      if (sa_frag) {
-        AttnFragParams a{};
-        a.q = qkv; a.ldq = C;
-        a.kf_hi = kf.hi; a.kf_lo = kf.lo; a.vf_hi = vf.hi; a.vf_lo = vf.lo;
-        const int nT = Tp / 32;
-        a.k_b = nT * (C / 16); a.k_h = dh / 16; a.k_t = C / 16;
-        a.v_b = nT * (C / 32) * 2; a.v_h = 0; a.v_t = (C / 32) * 2; a.v_kb = 1; a.v_nb = 2; a.self_layout = 1;
-        a.bias = nullptr; a.bias_ld = 0;
-        ao = attention_frag(ops, a, Tp, Tn, C);       // (queries: every row of the padded space; keys: the frames that exist)
-        release(kf); release(vf);
-      } else ao = attention(ops, qkv, 3 * C, qkv + C, qkv + 2 * C, 3 * C, nullptr, Tp, Tn, C, Tp);
-      release(qkv);
-      if (xa_ok(Tp, C) && cross_frag.count(p)) {
-        // chain 2 with the cross attention inside: to_out + residual -> LN2 -> to_q -> cross attention (wave = head, K / V
-        // of the prompt as hoisted MFMA fragments) -> to_out + residual -> LN3 partials   (4 launches -> 1)
-        if (!frag(w_o2)) return Act{};
-        float* h2 = alloc((size_t)M * C);
-        h3 = alloc((size_t)M * C);
-        l3 = LnIn{};
-        l3.pl = alloc_planes((size_t)M * C);
-        l3.stat = alloc((size_t)M * nblk * 2);
-        {
-          const XFrag& xf = cross_frag[p];
-          ChainParams cp{};
-          cp.M = M; cp.C = C; cp.T = Tp; cp.Tv = Tn; cp.amode = 0;
-          cp.a_hi = ao.hi; cp.a_lo = ao.lo;
-          cp.w1_hi = w_o1->fhi; cp.w1_lo = w_o1->flo; cp.Kp1 = w_o1->Kp; cp.b1 = w_o1->bias; cp.res = h; cp.out1 = h2;
-          cp.w2_hi = w_q2->fhi; cp.w2_lo = w_q2->flo; cp.Kp2 = w_q2->Kp; cp.b2 = w_q2->bias; cp.u2 = w_q2->u;
-          cp.passes = 1; cp.out2 = nullptr; cp.ldo2 = C; cp.ln_eps = 1e-5f;
-          cp.xa_kf_hi = xf.kf_hi; cp.xa_kf_lo = xf.kf_lo; cp.xa_vf_hi = xf.vf_hi; cp.xa_vf_lo = xf.vf_lo; cp.xa_bias = xbias;
-          cp.xa_nT = (L + 31) / 32; cp.xa_d = C / u->cfg.num_heads;
-          cp.xa_qscale = (1.0f / sqrtf((float)cp.xa_d)) * 1.44269504088896340736f;
-          cp.w3_hi = w_o2->fhi; cp.w3_lo = w_o2->flo; cp.b3 = w_o2->bias;
-          cp.out3 = h3; cp.out3_hi = l3.pl.hi; cp.out3_lo = l3.pl.lo; cp.rowstat3 = l3.stat;
-          {   // C = 256 with few row blocks (M = 4096 at the bench shape: 128 for 256 CUs): two workgroups per row block, heads
-              // 0-3 / 4-7, two waves per head, stage 3 handed over like a fused split-K pair (DVITS_CHAIN_XSPLIT=0: one)
-            const char* es = getenv("DVITS_CHAIN_XSPLIT");
-            const int rbs = M / 32, cus = n_cu > 0 ? n_cu : 256;
-            if (!(es && es[0] == '0') && C == 256 && rbs * 2 <= cus && rbs <= 4096 && (dry || u->sk_tickets)) {
-              cp.nsplit = 2;
-              cp.xs_buf = alloc((size_t)rbs * 2 * C * 32);
-              cp.xs_ticket = dry ? reinterpret_cast<unsigned*>(0x1000) : u->sk_tickets;
-            }
-          }
-          // The same block as ONE column-split launch of 64-row blocks (k_qkv_split MODE 2, kernels_qkv.hip: the slice's heads attend
-          // inside, h2 and the attention output handed over through the XCD's L2): one round of workgroups, whole multiples of 8
-          // row blocks (DVITS_QKV_XA=0: the row-block chain above)
-          ChainParams cq = cp;
-          cq.nsplit = 1; cq.xs_buf = nullptr; cq.xs_ticket = nullptr;
-          Planes oxa;
-          const int n_wg = (M / 64) * (C / 64);
-          bool split_xa = qkv_split_on && qkv_xa_on && C >= qkv_xa_min_c && gnx_on && u->exclusive && !arena.exact && !autotune_on() && n_cu > 0 &&
-                          Tp % 64 == 0 && (M / 64) % 8 == 0 && n_wg <= n_cu && n_wg >= qkv_split_min_wg && u->cfg.num_heads == 8 &&
-                          gnx_used + (size_t)2 * n_wg <= dv_unet::GNX_POOL;
-          if (split_xa) {
-            oxa = alloc_planes((size_t)M * C);
-            cq.qs_o_hi = oxa.hi; cq.qs_o_lo = oxa.lo;
-            split_xa = qkv_split_supported(cq, prec);
-            if (!split_xa) release(oxa);
-          }
-          if (split_xa) {
-            const int n_qflags = qkv_split_flags(cq);
-            cq.qs_flags = dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used;
-            cq.qs_status = dry ? reinterpret_cast<unsigned*>(0x1000) : u->gnx_status;
-            cq.qs_spin = gnx_spin;
-            gnx_used += ((size_t)n_qflags + 1) & ~(size_t)1;
-            if (!dry) { u->gnx_words = gnx_used; u->gnx_ops++; }
-            if (cp.xs_buf) { release(cp.xs_buf); cp.xs_buf = nullptr; }
-            cur_kind = "chain";
-            cur_flops = 2.0 * (double)M * C * C * 2.0 + 4.0 * B * u->cfg.num_heads * (double)Tp * L * cq.xa_d + 2.0 * (double)M * C * C;
-            char buf[96];
-            snprintf(buf, sizeof(buf), "to_out+res+LN+to_q+xattn+to_out+res (%d wg / 64 rows) M=%d C=%d", C / 64, M, C);
-            cur_desc = buf;
-            if (!dry) u->flops += cur_flops;
-            const int pr = prec;
-            emit(ops, [cq, pr](hipStream_t st) { return launch_qkv_split(cq, pr, st); });
-            release(oxa);
-          } else {
-          chain(ops, cp, cp.nsplit == 2 ? "to_out+res+LN+to_q+xattn(2 wg)+to_out+res" : "to_out+res+LN+to_q+xattn+to_out+res",
-                4.0 * B * u->cfg.num_heads * (double)Tp * L * cp.xa_d + 2.0 * (double)M * C * C);
-          if (cp.xs_buf) release(cp.xs_buf);
-          }
-        }
-        release(ao); release(h);
-        probe(tb + "attn1", h2, Tn, C);
-        release(h2);
-        probe(tb + "attn2", h3, Tn, C);
-      } else {
-      // chain 2: to_out + residual -> LN2 -> to_q of the cross attention   (2 launches -> 1)
+    if (chain_ok(b.Tp, C) && x.stat16) {
+      if (!(frag(b.w_in) && frag(b.w_qkv) && frag(b.w_o1) && frag(b.w_q2))) return Act{};
+      float* h = nullptr;
+      const Planes ao = xf_head(ops, b, h);
+      if (!xf_tail(ops, b, h, ao, h3, l3)) return Act{};
+    } else h3 = xf_attention_gemms(ops, b, l3);
+    return xf_ff(ops, b, h3, l3, want_planes);
+  }
+
+  // The block head as ONE launch, chain 1: GN(eps 1e-6) -> proj_in -> LN1 -> to_q | to_k | to_v   (3 launches -> 1), then the
+  // self attention.  h: proj_in's output (the block's first residual); returns the attention output.
+  Planes xf_head(std::vector<OpFn>& ops, const Xf& b, float*& h) {
+    const int C = b.C, Tn = b.Tn, Tp = b.Tp, M = b.M;
+    h = alloc((size_t)M * C);
+    // K and V leave the chain as MFMA fragments of 32-key tiles (k_attention_frag multiplies them as they are):
+    // DVITS_ATTN_FRAG=0 restores fp32 q | k | v and the converting attention kernel
+    const int dh = C / u->cfg.num_heads;
+    const bool sa_frag = attn_frag_on && !arena.exact && C % u->cfg.num_heads == 0 && dh % 16 == 0 && dh <= 64;
+    float* qkv = alloc((size_t)M * (sa_frag ? 1 : 3) * C);
+    Planes kf, vf;
+    if (sa_frag) { kf = alloc_planes((size_t)M * C); vf = alloc_planes((size_t)M * C); }
+    ChainParams cp{};
+    cp.M = M; cp.C = C; cp.T = Tp; cp.Tv = Tn; cp.amode = 1;
+    cp.x = b.x.p; cp.stat16 = b.x.stat16; cp.gamma = W(b.p + "norm.weight"); cp.beta = W(b.p + "norm.bias"); cp.gn_eps = 1e-6f;
+    cp.groups = u->cfg.norm_num_groups;
+    cp.w1_hi = b.w_in->fhi; cp.w1_lo = b.w_in->flo; cp.Kp1 = b.w_in->Kp; cp.b1 = b.w_in->bias; cp.res = nullptr; cp.out1 = h;
+    cp.w2_hi = b.w_qkv->fhi; cp.w2_lo = b.w_qkv->flo; cp.Kp2 = b.w_qkv->Kp; cp.b2 = b.w_qkv->bias; cp.u2 = b.w_qkv->u;
+    cp.passes = 3; cp.out2 = qkv; cp.ldo2 = sa_frag ? C : 3 * C; cp.ln_eps = 1e-5f;
+    if (sa_frag) { cp.sa_kf_hi = kf.hi; cp.sa_kf_lo = kf.lo; cp.sa_vf_hi = vf.hi; cp.sa_vf_lo = vf.lo; }
+    {   // few row blocks: share the three passes out (DVITS_CHAIN_SPLIT=0: one workgroup per row block)
+      const int rbs = M / 32, cus = n_cu > 0 ? n_cu : 256;
+      cp.nsplit = !chain_split_on ? 1 : (rbs * 3 <= cus ? 3 : (rbs * 2 <= cus ? 2 : 1));
+    }
+    // 64-row blocks with the output columns of both contractions split over C / 64 workgroups per row block (k_qkv_split,
+    // kernels_qkv.hip: an all-gather of h inside the launch - planned like k_ff_split's hand-over; DVITS_QKV_SPLIT=0: the
+    // 32-row chain above) wherever that gives the launch at least qkv_split_min_wg workgroups
+    const int n_qflags = qkv_split_flags(cp);
+    const bool split = qkv_split_on && C >= qkv_split_min_c && sa_frag && handover_ok() && !autotune_on() &&
+                       n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL &&   // (one round of workgroups: at B = 16 - 384 / 512 of them - the 32-row chain is the faster one, 4.09 vs 4.19 ms per forward)
+                       qkv_split(ops, cp, strf("norm+proj_in+LN+q|Kfrag|Vfrag (%d wg / 64 rows) M=%d C=%d N2=%d", C / 64, M, C, 3 * C));
+    if (!split) chain(ops, cp, sa_frag ? "norm+proj_in+LN+q|Kfrag|Vfrag" : "norm+proj_in+LN+qkv");
+    probe(b.p + "proj_in", h, Tn, C);
+    Planes ao;
+    if (sa_frag) {
+      AttnFragParams a{};
+      a.q = qkv; a.ldq = C;
+      a.kf_hi = kf.hi; a.kf_lo = kf.lo; a.vf_hi = vf.hi; a.vf_lo = vf.lo;
+      const int nT = Tp / 32;
+      a.k_b = nT * (C / 16); a.k_h = dh / 16; a.k_t = C / 16;
+      a.v_b = nT * (C / 32) * 2; a.v_h = 0; a.v_t = (C / 32) * 2; a.v_kb = 1; a.v_nb = 2; a.self_layout = 1;
+      a.bias = nullptr; a.bias_ld = 0;
+      ao = attention_frag(ops, a, Tp, Tn, C);       // (queries: every row of the padded space; keys: the frames that exist)
+      release(kf); release(vf);
+    } else ao = attention(ops, qkv, 3 * C, qkv + C, qkv + 2 * C, 3 * C, nullptr, Tp, Tn, C, Tp);
+    release(qkv);
+    return ao;
+  }
+
+  // The chained block's attention tail: to_out + residual h -> LN2 -> to_q, the cross attention (inside the launch, or after
+  // it) -> to_out + residual -> h3 + LN3 partials l3.  Consumes h and the self attention's output ao.
+  bool xf_tail(std::vector<OpFn>& ops, const Xf& b, float* h, Planes ao, float*& h3, LnIn& l3) {
+    const int C = b.C, M = b.M;
+    if (xa_ok(b.Tp, C) && cross_frag.count(b.p)) {
+      if (!frag(b.w_o2)) return false;
       float* h2 = alloc((size_t)M * C);
-      float* q2 = alloc((size_t)M * C);
-      {
-        ChainParams cp{};
-        cp.M = M; cp.C = C; cp.T = Tp; cp.Tv = Tn; cp.amode = 0;
-        cp.a_hi = ao.hi; cp.a_lo = ao.lo;
-        cp.w1_hi = w_o1->fhi; cp.w1_lo = w_o1->flo; cp.Kp1 = w_o1->Kp; cp.b1 = w_o1->bias; cp.res = h; cp.out1 = h2;
-        cp.w2_hi = w_q2->fhi; cp.w2_lo = w_q2->flo; cp.Kp2 = w_q2->Kp; cp.b2 = w_q2->bias; cp.u2 = w_q2->u;
-        cp.passes = 1; cp.out2 = q2; cp.ldo2 = C; cp.ln_eps = 1e-5f;
-        {   // few row blocks: the 128-column groups of to_q are shared out over C / 128 workgroups per row block
-          const char* es = getenv("DVITS_CHAIN_SPLIT");
-          const bool off = es && es[0] == '0';
-          const int rbs = M / 32, cus = n_cu > 0 ? n_cu : 256, nsg = C / 128;
-          cp.nsplit = (!off && nsg >= 2 && rbs * nsg <= cus) ? nsg : 1;
-        }
-        // (the same 64-row column-split launch as the block head - k_qkv_split, MODE 1: one round of workgroups)
-        const int n_qflags = qkv_split_flags(cp);
-        if (qkv_split_on && C >= qkv_split_min_c && gnx_on && u->exclusive && !arena.exact && !autotune_on() && n_cu > 0 && qkv_split_supported(cp, prec) &&
-            n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL) {
-          cp.nsplit = 1;
-          cp.qs_flags = dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used;
-          cp.qs_status = dry ? reinterpret_cast<unsigned*>(0x1000) : u->gnx_status;
-          cp.qs_spin = gnx_spin;
-          gnx_used += ((size_t)n_qflags + 1) & ~(size_t)1;
-          if (!dry) { u->gnx_words = gnx_used; u->gnx_ops++; }
-          cur_kind = "chain";
-          cur_flops = 2.0 * (double)cp.M * cp.C * cp.C * 2.0;
-          char buf[96];
-          snprintf(buf, sizeof(buf), "to_out+res+LN+to_q (%d wg / 64 rows) M=%d C=%d N2=%d", C / 64, cp.M, cp.C, cp.C);
-          cur_desc = buf;
-          if (!dry) u->flops += cur_flops;
-          const int pr = prec;
-          emit(ops, [cp, pr](hipStream_t st) { return launch_qkv_split(cp, pr, st); });
-        } else
-        chain(ops, cp, "to_out+res+LN+to_q");
-      }
-      release(ao); release(h);
-      probe(tb + "attn1", h2, Tn, C);
-      float* kv = cross_kv[p];
-      if (attn_frag_on && !arena.exact && cross_frag.count(p)) ao = cross_attention_frag(ops, p, q2, Tp, C);
-      else ao = attention(ops, q2, C, kv, kv + C, 2 * C, mask_bias, Tp, L, C);
-      release(q2);
       h3 = alloc((size_t)M * C);
-      {
-        GemmParams g = gp_base(Tn, M, C); g.seg[0] = seg(ao, C, Planes{}, 0, 1, 0);
-        g.epi = EPI_RESIDUAL; g.res = h2; g.out = h3; l3 = ln_produce(g);
-        gemm(ops, g, w_o2, C);
+      l3 = ln_planes(M, C);
+      xf_xattn_chain(ops, b, h, ao, h2, h3, l3);
+      release(ao); release(h);
+      probe(b.tb + "attn1", h2, b.Tn, C);
+      release(h2);
+      probe(b.tb + "attn2", h3, b.Tn, C);
+      return true;
+    }
+    // chain 2: to_out + residual -> LN2 -> to_q of the cross attention   (2 launches -> 1)
+    float* h2 = alloc((size_t)M * C);
+    float* q2 = alloc((size_t)M * C);
+    ChainParams cp = tail_chain(b, h, ao, h2);
+    cp.out2 = q2;
+    {   // few row blocks: the 128-column groups of to_q are shared out over C / 128 workgroups per row block
+      const int rbs = M / 32, cus = n_cu > 0 ? n_cu : 256, nsg = C / 128;
+      cp.nsplit = (chain_split_on && nsg >= 2 && rbs * nsg <= cus) ? nsg : 1;
+    }
+    // (the same 64-row column-split launch as the block head - k_qkv_split, MODE 1: one round of workgroups)
+    const int n_qflags = qkv_split_flags(cp);
+    const bool split = qkv_split_on && C >= qkv_split_min_c && handover_ok() && !autotune_on() &&
+                       n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL &&
+                       qkv_split(ops, cp, strf("to_out+res+LN+to_q (%d wg / 64 rows) M=%d C=%d N2=%d", C / 64, M, C, C));
+    if (!split) chain(ops, cp, "to_out+res+LN+to_q");
+    release(ao); release(h);
+    probe(b.tb + "attn1", h2, b.Tn, C);
+    h3 = cross_attention_out(ops, b, q2, h2, l3);
+    return true;
+  }
+  // what both forms of chain 2 compute first: to_out over the attention output ao + residual h -> h2 -> LN2 -> to_q
+  ChainParams tail_chain(const Xf& b, float* h, Planes ao, float* h2) {
+    ChainParams cp{};
+    cp.M = b.M; cp.C = b.C; cp.T = b.Tp; cp.Tv = b.Tn; cp.amode = 0;
+    cp.a_hi = ao.hi; cp.a_lo = ao.lo;
+    cp.w1_hi = b.w_o1->fhi; cp.w1_lo = b.w_o1->flo; cp.Kp1 = b.w_o1->Kp; cp.b1 = b.w_o1->bias; cp.res = h; cp.out1 = h2;
+    cp.w2_hi = b.w_q2->fhi; cp.w2_lo = b.w_q2->flo; cp.Kp2 = b.w_q2->Kp; cp.b2 = b.w_q2->bias; cp.u2 = b.w_q2->u;
+    cp.passes = 1; cp.out2 = nullptr; cp.ldo2 = b.C; cp.ln_eps = 1e-5f;
+    return cp;
+  }
+  // chain 2 with the cross attention inside: to_out + residual -> LN2 -> to_q -> cross attention (wave = head, K / V
+  // of the prompt as hoisted MFMA fragments) -> to_out + residual -> LN3 partials   (4 launches -> 1)
+  void xf_xattn_chain(std::vector<OpFn>& ops, const Xf& b, float* h, Planes ao, float* h2, float* h3, const LnIn& l3) {
+    const int C = b.C, Tp = b.Tp, M = b.M;
+    const XFrag& xf = cross_frag[b.p];
+    ChainParams cp = tail_chain(b, h, ao, h2);
+    cp.xa_kf_hi = xf.kf_hi; cp.xa_kf_lo = xf.kf_lo; cp.xa_vf_hi = xf.vf_hi; cp.xa_vf_lo = xf.vf_lo; cp.xa_bias = xbias;
+    cp.xa_nT = (L + 31) / 32; cp.xa_d = C / u->cfg.num_heads;
+    cp.xa_qscale = (1.0f / sqrtf((float)cp.xa_d)) * 1.44269504088896340736f;
+    cp.w3_hi = b.w_o2->fhi; cp.w3_lo = b.w_o2->flo; cp.b3 = b.w_o2->bias;
+    cp.out3 = h3; cp.out3_hi = l3.pl.hi; cp.out3_lo = l3.pl.lo; cp.rowstat3 = l3.stat;
+    {   // C = 256 with few row blocks (M = 4096 at the bench shape: 128 for 256 CUs): two workgroups per row block, heads
+        // 0-3 / 4-7, two waves per head, stage 3 handed over like a fused split-K pair (DVITS_CHAIN_XSPLIT=0: one)
+      const int rbs = M / 32, cus = n_cu > 0 ? n_cu : 256;
+      if (chain_xsplit_on && C == 256 && rbs * 2 <= cus && rbs <= 4096 && (dry || u->sk_tickets)) {
+        cp.nsplit = 2;
+        cp.xs_buf = alloc((size_t)rbs * 2 * C * 32);
+        cp.xs_ticket = dry ? reinterpret_cast<unsigned*>(0x1000) : u->sk_tickets;
       }
-      release(ao); release(h2);
-      probe(tb + "attn2", h3, Tn, C);
-      }
-    } else {
+    }
+    // The same block as ONE column-split launch of 64-row blocks (k_qkv_split MODE 2, kernels_qkv.hip: the slice's heads attend
+    // inside, h2 and the attention output handed over through the XCD's L2): one round of workgroups, whole multiples of 8
+    // row blocks (DVITS_QKV_XA=0: the row-block chain above)
+    ChainParams cq = cp;
+    cq.nsplit = 1; cq.xs_buf = nullptr; cq.xs_ticket = nullptr;
+    const double xattn_flops = 4.0 * B * u->cfg.num_heads * (double)Tp * L * cp.xa_d + 2.0 * (double)M * C * C;
+    const int n_wg = (M / 64) * (C / 64);
+    bool split_xa = qkv_split_on && qkv_xa_on && C >= qkv_xa_min_c && handover_ok() && !autotune_on() &&
+                    Tp % 64 == 0 && (M / 64) % 8 == 0 && n_wg <= n_cu && n_wg >= qkv_split_min_wg && u->cfg.num_heads == 8 &&
+                    gnx_used + (size_t)2 * n_wg <= dv_unet::GNX_POOL;
+    Planes oxa;
+    if (split_xa) {
+      oxa = alloc_planes((size_t)M * C);
+      cq.qs_o_hi = oxa.hi; cq.qs_o_lo = oxa.lo;
+      split_xa = qkv_split(ops, cq, strf("to_out+res+LN+to_q+xattn+to_out+res (%d wg / 64 rows) M=%d C=%d", C / 64, M, C), xattn_flops);
+      if (!split_xa) release(oxa);
+    }
+    if (!split_xa)
+      chain(ops, cp, cp.nsplit == 2 ? "to_out+res+LN+to_q+xattn(2 wg)+to_out+res" : "to_out+res+LN+to_q+xattn+to_out+res", xattn_flops);
+    if (cp.xs_buf) release(cp.xs_buf);
+    if (split_xa) release(oxa);
+  }
+
+  // The block's attention as one launch per GEMM (DVITS_CHAIN=0, or channel counts the row-block chains do not take); returns
+  // h3 and its LN3 partials l3
+  float* xf_attention_gemms(std::vector<OpFn>& ops, const Xf& b, LnIn& l3) {
+    const int C = b.C, Tn = b.Tn, Tp = b.Tp, M = b.M;
     // GN(eps 1e-6) -> 1x1 proj_in
     float* h = alloc((size_t)M * C);
     LnIn l1;
     {
       GemmParams g = gp_base(Tn, M, C);
-      g.out = h; l1 = ln_produce(g);
-      {
-        Planes gn;
-        if (x.n_hi && x.n_pre == p + "norm") { gn.hi = x.n_hi; gn.lo = x.n_lo; }    // normalised by its producer's epilogue
-        else gn = norm_apply(ops, x, Act{}, p + "norm", 1e-6f, nullptr, nullptr, 0, false, nullptr);
-        g.seg[0] = seg(gn, C, Planes{}, 0, 1, 0);
-        gemm(ops, g, w_in, C);
-        release(gn);
-      }
+      g.out = h; l1 = ln_produce(g, M, C);
+      Planes gn;
+      if (b.x.n_hi && b.x.n_pre == b.p + "norm") { gn.hi = b.x.n_hi; gn.lo = b.x.n_lo; }    // normalised by its producer's epilogue
+      else gn = norm_apply(ops, b.x, Act{}, b.p + "norm", 1e-6f, nullptr, nullptr, 0, false, nullptr);
+      g.seg[0] = seg(gn, C, Planes{}, 0, 1, 0);
+      gemm(ops, g, b.w_in, C);
+      release(gn);
     }
-    probe(p + "proj_in", h, Tn, C);
+    probe(b.p + "proj_in", h, Tn, C);
 
     // self-attention
     float* qkv = alloc((size_t)M * 3 * C);
     {
       GemmParams g = gp_base(Tn, M, 3 * C);
-      g.out = qkv; ln_consume(g, l1, h, w_qkv); gemm(ops, g, w_qkv, C);
+      g.out = qkv; ln_consume(ops, g, l1, h, b.w_qkv, M, C); gemm(ops, g, b.w_qkv, C);
     }
     ln_release(l1);
     Planes ao = attention(ops, qkv, 3 * C, qkv + C, qkv + 2 * C, 3 * C, nullptr, Tp, Tn, C, Tp);   // (keys: the frames that exist)
@@ -1344,163 +1309,130 @@ struct Builder {
     LnIn l2;
     {
       GemmParams g = gp_base(Tn, M, C); g.seg[0] = seg(ao, C, Planes{}, 0, 1, 0);
-      g.epi = EPI_RESIDUAL; g.res = h; g.out = h2; l2 = ln_produce(g);
-      gemm(ops, g, w_o1, C);
+      g.epi = EPI_RESIDUAL; g.res = h; g.out = h2; l2 = ln_produce(g, M, C);
+      gemm(ops, g, b.w_o1, C);
     }
     release(ao); release(h);
-    probe(tb + "attn1", h2, Tn, C);
+    probe(b.tb + "attn1", h2, Tn, C);
 
-    // cross-attention (K/V hoisted: projected once per set_cond)
     float* q2 = alloc((size_t)M * C);
     {
       GemmParams g = gp_base(Tn, M, C);
-      g.out = q2; ln_consume(g, l2, h2, w_q2); gemm(ops, g, w_q2, C);
+      g.out = q2; ln_consume(ops, g, l2, h2, b.w_q2, M, C); gemm(ops, g, b.w_q2, C);
     }
     ln_release(l2);
-    float* kv = cross_kv[p];
-    if (attn_frag_on && !arena.exact && cross_frag.count(p)) ao = cross_attention_frag(ops, p, q2, Tp, C);
+    return cross_attention_out(ops, b, q2, h2, l3);
+  }
+  // cross-attention (K/V hoisted: projected once per set_cond) of the query q2, then to_out + residual h2 -> h3 (returned) and
+  // its LN3 partials l3.  Consumes q2 and h2.
+  float* cross_attention_out(std::vector<OpFn>& ops, const Xf& b, float* q2, float* h2, LnIn& l3) {
+    const int C = b.C, Tp = b.Tp, M = b.M;
+    float* kv = cross_kv[b.p];
+    Planes ao;
+    if (attn_frag_on && !arena.exact && cross_frag.count(b.p)) ao = cross_attention_frag(ops, b.p, q2, Tp, C);
     else ao = attention(ops, q2, C, kv, kv + C, 2 * C, mask_bias, Tp, L, C);
     release(q2);
-    h3 = alloc((size_t)M * C);
+    float* h3 = alloc((size_t)M * C);
     {
-      GemmParams g = gp_base(Tn, M, C); g.seg[0] = seg(ao, C, Planes{}, 0, 1, 0);
-      g.epi = EPI_RESIDUAL; g.res = h2; g.out = h3; l3 = ln_produce(g);
-      gemm(ops, g, w_o2, C);
+      GemmParams g = gp_base(b.Tn, M, C); g.seg[0] = seg(ao, C, Planes{}, 0, 1, 0);
+      g.epi = EPI_RESIDUAL; g.res = h2; g.out = h3; l3 = ln_produce(g, M, C);
+      gemm(ops, g, b.w_o2, C);
     }
     release(ao); release(h2);
-    probe(tb + "attn2", h3, Tn, C);
-    }
+    probe(b.tb + "attn2", h3, b.Tn, C);
+    return h3;
+  }
 
+  // The block's feed-forward: LN3 -> GEGLU -> ff.net.2 + residual h3 -> proj_out + the block input x.  Consumes h3 and l3.
+  Act xf_ff(std::vector<OpFn>& ops, const Xf& b, float* h3, LnIn& l3, bool want_planes) {
+    const int C = b.C, Tp = b.Tp, M = b.M;
+    const bool one_launch = b.merged_ffproj && chain_on && !arena.exact && l3.stat && b.x.stat16;
     // C = 128 blocks: LN3 -> GEGLU -> merged ff.net.2 + proj_out + residual as ONE row-block launch (k_chain_ff; the
     // 4C-wide product never leaves LDS).  DVITS_CHAIN_FF=0 restores the two GEMMs.
-    {
-      const char* eff = getenv("DVITS_CHAIN_FF");
-      const bool ff_off = eff && eff[0] == '0';
-      ChainFFParams fp{};
-      fp.M = M; fp.C = C; fp.T = Tp; fp.Tv = Tn;
-      if (!ff_off && merged_ffproj && chain_on && !arena.exact && l3.stat && x.stat16 && chain_ff_supported(fp, prec)) {
-        const std::string mw = tb + "__ffproj.weight", mb = tb + "__ffproj.bias";
-        if (!dry && !u->packed.count(p + "ffproj")) {
-          const float* Wo = W(p + "proj_out.weight"); const float* W2 = W(tb + "ff.net.2.weight");
-          const float* bo = W(p + "proj_out.bias"); const float* b2 = W(tb + "ff.net.2.bias");
-          float* dw = derived(mw, {C, 4 * C});
-          float* db = derived(mb, {C});
-          if (!Wo || !W2 || !bo || !b2 || !dw || !db) return Act{};
-          (void)launch_matmul_f32(Wo, W2, dw, C, C, 4 * C, pack_stream);
-          (void)launch_fold_bias(Wo, bo, b2, db, C, C, 0, 0, pack_stream);
-        }
-        const PackedW* w_m = pack(p + "ffproj", C, 5 * C, {{p + "proj_out.weight", 1, C, 1, C, 0, 0, "", 0}, {mw, 0, 4 * C, 1, 4 * C, C, 0, "", 0}},
-                                  {{mb, "", "", "", C, 0, 0, 0}});
-        if (!w_m || !frag(w_gg) || !frag(w_m)) return Act{};
-        Act out{};
-        out.p = alloc((size_t)M * C); out.C = C; out.T = Tn; out.Tp = Tp; alloc_stat(out, true);
-        fp.a_hi = l3.pl.hi; fp.a_lo = l3.pl.lo; fp.rowstat = l3.stat; fp.ln_eps = 1e-5f;
-        fp.wg_hi = w_gg->fhi; fp.wg_lo = w_gg->flo; fp.bg = w_gg->bias; fp.ug = w_gg->u;
-        fp.wm_hi = w_m->fhi; fp.wm_lo = w_m->flo; fp.bm = w_m->bias;
-        fp.res = x.p; fp.out = out.p; fp.stats16 = out.stat16;
-        if (want_planes) {
-          Planes pl = alloc_planes((size_t)M * C);
-          out.pl_hi = pl.hi; out.pl_lo = pl.lo; fp.out_hi = pl.hi; fp.out_lo = pl.lo;
-        }
-        offer_next(fp, out);
-        cur_kind = "chain";
-        cur_flops = 2.0 * (double)M * C * (8.0 * C + 5.0 * C);
-        {
-          char buf[96];
-          snprintf(buf, sizeof(buf), "LN+GEGLU+ffproj+res%s M=%d C=%d", fp.gnx.xchg ? "+gnx" : "", M, C);
-          cur_desc = buf;
-        }
-        if (!dry) u->flops += cur_flops;
-        const int pr = prec;
-        emit(ops, [fp, pr](hipStream_t st) { return launch_chain_ff(fp, pr, st); });
-        ln_release(l3);
-        release(h3);
-        probe(p.substr(0, p.size() - 1), out.p, Tn, C);
-        return out;
-      }
-    }
+    ChainFFParams cf{};
+    cf.M = M; cf.C = C; cf.T = Tp; cf.Tv = b.Tn;
     // C = 256 / 384 blocks: the same three steps as ONE launch of 64-row blocks whose product columns are split over 4 / 8
     // workgroups (k_ff_split, kernels_ffsplit.hip: partial ffproj sums handed over inside the launch - every workgroup resident,
     // like the in-launch GroupNorm; DVITS_FF_SPLIT=0 restores the two GEMMs)
-    {
-      FFSplitParams fp{};
-      fp.M = M; fp.C = C; fp.T = Tp; fp.Tv = Tn; fp.nspl = C == 256 ? 4 : 8;
-      const int ff_rows = fp.rows = ff_split_rows(C, M, Tp, fp.nspl, n_cu);   // 64 rows per workgroup; 32 at C = 512, odd pitches, small inputs
-      const size_t n_flags = (size_t)(M / ff_rows) * fp.nspl * 8;       // one word per wave (kernels_ffsplit.hip)
-      if (ff_split_on && merged_ffproj && chain_on && gnx_on && u->exclusive && !arena.exact && !autotune_on() && l3.stat && x.stat16 &&
-          n_cu > 0 && (C == 256 || C == 384 || C == 512) && ff_split_supported(fp, prec) && ((M / ff_rows) * fp.nspl <= n_cu || gemm_handover_rounds()) &&
-          (M / ff_rows) * fp.nspl >= ff_split_min_wg &&
-          gnx_used + n_flags <= dv_unet::GNX_POOL) {
-        const std::string mw = tb + "__ffproj.weight", mb = tb + "__ffproj.bias";
-        if (!dry && !u->packed.count(p + "ffproj")) {
-          const float* Wo = W(p + "proj_out.weight"); const float* W2 = W(tb + "ff.net.2.weight");
-          const float* bo = W(p + "proj_out.bias"); const float* b2 = W(tb + "ff.net.2.bias");
-          float* dw = derived(mw, {C, 4 * C});
-          float* db = derived(mb, {C});
-          if (!Wo || !W2 || !bo || !b2 || !dw || !db) return Act{};
-          (void)launch_matmul_f32(Wo, W2, dw, C, C, 4 * C, pack_stream);
-          (void)launch_fold_bias(Wo, bo, b2, db, C, C, 0, 0, pack_stream);
-        }
-        const PackedW* w_m = pack(p + "ffproj", C, 5 * C, {{p + "proj_out.weight", 1, C, 1, C, 0, 0, "", 0}, {mw, 0, 4 * C, 1, 4 * C, C, 0, "", 0}},
-                                  {{mb, "", "", "", C, 0, 0, 0}});
-        if (!w_m || !frag(w_gg) || !frag(w_m)) return Act{};
-        Act out{};
-        out.p = alloc((size_t)M * C); out.C = C; out.T = Tn; out.Tp = Tp; alloc_stat(out, true);
-        fp.a_hi = l3.pl.hi; fp.a_lo = l3.pl.lo; fp.rowstat = l3.stat; fp.ln_eps = 1e-5f;
-        fp.wg_hi = w_gg->fhi; fp.wg_lo = w_gg->flo; fp.bg = w_gg->bias; fp.ug = w_gg->u;
-        fp.wm_hi = w_m->fhi; fp.wm_lo = w_m->flo; fp.bm = w_m->bias;
-        fp.res = x.p; fp.out = out.p; fp.stats16 = out.stat16;
-        fp.flags = dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used;
-        fp.status = dry ? reinterpret_cast<unsigned*>(0x1000) : u->gnx_status;
-        fp.spin_max = gnx_spin;
-        gnx_used += n_flags;
-        if (!dry) { u->gnx_words = gnx_used; u->gnx_ops++; }
-        fp.xbuf = alloc(ff_split_xbuf_floats(M, C, fp.nspl, fp.rows));
-        if (want_planes) {
-          Planes pl = alloc_planes((size_t)M * C);
-          out.pl_hi = pl.hi; out.pl_lo = pl.lo; fp.out_hi = pl.hi; fp.out_lo = pl.lo;
-        }
-        offer_next(fp, out);
-        cur_kind = "chain";
-        cur_flops = 2.0 * (double)M * C * (8.0 * C + 5.0 * C);
-        {
-          char buf[96];
-          snprintf(buf, sizeof(buf), "LN+GEGLU+ffproj+res%s (%d wg / %d rows) M=%d C=%d", fp.gnx.xchg ? "+gnx" : "", fp.nspl, ff_rows, M, C);
-          cur_desc = buf;
-        }
-        if (!dry) u->flops += cur_flops;
-        const int pr = prec;
-        emit(ops, [fp, pr](hipStream_t st) { return launch_ff_split(fp, pr, st); });
-        release(fp.xbuf);
-        ln_release(l3);
-        release(h3);
-        probe(p.substr(0, p.size() - 1), out.p, Tn, C);
-        return out;
-      }
+    FFSplitParams fs{};
+    fs.M = M; fs.C = C; fs.T = Tp; fs.Tv = b.Tn; fs.nspl = C == 256 ? 4 : 8;
+    fs.rows = ff_split_rows(C, M, Tp, fs.nspl, n_cu);   // 64 rows per workgroup; 32 at C = 512, odd pitches, small inputs
+    const int ff_wg = (M / fs.rows) * fs.nspl;
+    const size_t n_flags = (size_t)ff_wg * 8;         // one word per wave (kernels_ffsplit.hip)
+    if (one_launch && chain_ff_on && chain_ff_supported(cf, prec)) return ff_launch(ops, b, cf, h3, l3, want_planes);
+    else if (one_launch && ff_split_on && handover_ok() && !autotune_on() && (C == 256 || C == 384 || C == 512) &&
+             ff_split_supported(fs, prec) && (ff_wg <= n_cu || gemm_handover_rounds()) && ff_wg >= ff_split_min_wg &&
+             gnx_used + n_flags <= dv_unet::GNX_POOL)
+      return ff_launch(ops, b, fs, h3, l3, want_planes);
+    else return xf_ff_gemms(ops, b, h3, l3, want_planes);
+  }
+  // ff.net.2 and proj_out merged into one weight over [h3 | GEGLU product] (see xf_ff_gemms): [proj_out | Wo W2], bias Wo b2 + bo
+  const PackedW* ffproj_weight(const Xf& b) {
+    const int C = b.C;
+    const std::string &p = b.p, &tb = b.tb;
+    const std::string mw = tb + "__ffproj.weight", mb = tb + "__ffproj.bias";
+    if (!dry && !u->packed.count(p + "ffproj")) {   // (kept across prepares with the packed weights)
+      const float* Wo = W(p + "proj_out.weight"); const float* W2 = W(tb + "ff.net.2.weight");
+      const float* bo = W(p + "proj_out.bias"); const float* b2 = W(tb + "ff.net.2.bias");
+      float* dw = derived(mw, {C, 4 * C});
+      float* db = derived(mb, {C});
+      if (!Wo || !W2 || !bo || !b2 || !dw || !db) return nullptr;
+      (void)launch_matmul_f32(Wo, W2, dw, C, C, 4 * C, pack_stream);
+      (void)launch_fold_bias(Wo, bo, b2, db, C, C, 0, 0, pack_stream);
     }
+    return pack(p + "ffproj", C, 5 * C, {{p + "proj_out.weight", 1, C, 1, C, 0, 0, "", 0}, {mw, 0, 4 * C, 1, 4 * C, C, 0, "", 0}},
+                {{mb, "", "", "", C, 0, 0, 0}});
+  }
+  // the feed-forward as ONE launch: k_chain_ff (ChainFFParams) or k_ff_split (FFSplitParams)
+  template <class FF> Act ff_launch(std::vector<OpFn>& ops, const Xf& b, FF fp, float* h3, LnIn& l3, bool want_planes) {
+    constexpr bool split = std::is_same<FF, FFSplitParams>::value;
+    const int C = b.C, M = b.M;
+    const PackedW* w_m = ffproj_weight(b);
+    if (!w_m || !frag(b.w_gg) || !frag(w_m)) return Act{};
+    Act out{};
+    out.p = alloc((size_t)M * C); out.C = C; out.T = b.Tn; out.Tp = b.Tp; alloc_stat(out, true);
+    fp.a_hi = l3.pl.hi; fp.a_lo = l3.pl.lo; fp.rowstat = l3.stat; fp.ln_eps = 1e-5f;
+    fp.wg_hi = b.w_gg->fhi; fp.wg_lo = b.w_gg->flo; fp.bg = b.w_gg->bias; fp.ug = b.w_gg->u;
+    fp.wm_hi = w_m->fhi; fp.wm_lo = w_m->flo; fp.bm = w_m->bias;
+    fp.res = b.x.p; fp.out = out.p; fp.stats16 = out.stat16;
+    if constexpr (split) {
+      const Handover ho = handover((size_t)(M / fp.rows) * fp.nspl * 8);
+      fp.flags = ho.flags; fp.status = ho.status; fp.spin_max = gnx_spin;
+      fp.xbuf = alloc(ff_split_xbuf_floats(M, C, fp.nspl, fp.rows));
+    }
+    if (want_planes) out_planes(fp, out);
+    offer_next(fp, out);
+    const double flops = 2.0 * (double)M * C * (8.0 * C + 5.0 * C);
+    const char* gnx = fp.gnx.xchg ? "+gnx" : "";
+    const int pr = prec;
+    if constexpr (split) {
+      emit_launch(ops, "chain", flops, strf("LN+GEGLU+ffproj+res%s (%d wg / %d rows) M=%d C=%d", gnx, fp.nspl, fp.rows, M, C),
+                  [fp, pr](hipStream_t st) { return launch_ff_split(fp, pr, st); });
+      release(fp.xbuf);
+    } else {
+      emit_launch(ops, "chain", flops, strf("LN+GEGLU+ffproj+res%s M=%d C=%d", gnx, M, C),
+                  [fp, pr](hipStream_t st) { return launch_chain_ff(fp, pr, st); });
+    }
+    ln_release(l3);
+    release(h3);
+    probe(b.p.substr(0, b.p.size() - 1), out.p, b.Tn, C);
+    return out;
+  }
+  // the feed-forward as GEMMs: GEGLU, then the merged ffproj GEMM or ff.net.2 and proj_out
+  Act xf_ff_gemms(std::vector<OpFn>& ops, const Xf& b, float* h3, LnIn& l3, bool want_planes) {
+    const int C = b.C, Tn = b.Tn, Tp = b.Tp, M = b.M;
     // GEGLU feed-forward: the GEGLU product and the FF output only feed GEMMs -> split planes only
     Planes gg = alloc_planes((size_t)M * 4 * C);
     {
       GemmParams g = gp_base(Tn, M, 8 * C);
-      g.epi = EPI_GEGLU; g.out_hi = gg.hi; g.out_lo = gg.lo; g.ldo = 4 * C; ln_consume(g, l3, h3, w_gg); gemm(ops, g, w_gg, C);
+      g.epi = EPI_GEGLU; g.out_hi = gg.hi; g.out_lo = gg.lo; g.ldo = 4 * C; ln_consume(ops, g, l3, h3, b.w_gg, M, C); gemm(ops, g, b.w_gg, C);
     }
     // ff.net.2 and proj_out are two k=1 contractions with only the residual add between them:
     //   proj_out(h3 + gg W2^T + b2) + x = h3 Wo^T + gg (Wo W2)^T + (Wo b2 + bo) + x
     // -> ONE contraction over two K-segments [raw planes of h3 | GEGLU product] (16 launches fewer per forward).
     // Needs the raw h3 planes of the fused-LayerNorm schedule; the per-layer probe build keeps the two-step form.
-    if (merged_ffproj) {
-      const std::string mw = tb + "__ffproj.weight", mb = tb + "__ffproj.bias";
-      if (!dry && !u->packed.count(p + "ffproj")) {   // (kept across prepares with the packed weights)
-        const float* Wo = W(p + "proj_out.weight"); const float* W2 = W(tb + "ff.net.2.weight");
-        const float* bo = W(p + "proj_out.bias"); const float* b2 = W(tb + "ff.net.2.bias");
-        float* dw = derived(mw, {C, 4 * C});
-        float* db = derived(mb, {C});
-        if (!Wo || !W2 || !bo || !b2 || !dw || !db) return Act{};
-        (void)launch_matmul_f32(Wo, W2, dw, C, C, 4 * C, pack_stream);
-        (void)launch_fold_bias(Wo, bo, b2, db, C, C, 0, 0, pack_stream);
-      }
-      const PackedW* w_m = pack(p + "ffproj", C, 5 * C, {{p + "proj_out.weight", 1, C, 1, C, 0, 0, "", 0}, {mw, 0, 4 * C, 1, 4 * C, C, 0, "", 0}},
-                                {{mb, "", "", "", C, 0, 0, 0}});
+    if (b.merged_ffproj) {
+      const PackedW* w_m = ffproj_weight(b);
       if (!w_m) return Act{};
       Act out{};
       out.p = alloc((size_t)M * C); out.C = C; out.T = Tn; out.Tp = Tp; alloc_stat(out);
@@ -1508,17 +1440,14 @@ struct Builder {
         GemmParams g = gp_base(Tn, M, C);
         g.seg[0] = seg(l3.pl, C, Planes{}, 0, 1, 0);
         g.seg[1] = seg(gg, 4 * C, Planes{}, 0, 1, 0); g.nseg = 2;
-        g.epi = EPI_RESIDUAL; g.res = x.p; g.out = out.p; stat_out(g, out);
-        if (want_planes) {
-          Planes pl = alloc_planes((size_t)M * C);
-          out.pl_hi = pl.hi; out.pl_lo = pl.lo; g.out_hi = pl.hi; g.out_lo = pl.lo;
-        }
+        g.epi = EPI_RESIDUAL; g.res = b.x.p; g.out = out.p; stat_out(g, out);
+        if (want_planes) out_planes(g, out);
         offer_next(g, out);
         gemm(ops, g, w_m, 5 * C);
       }
       ln_release(l3);
       release(gg); release(h3);
-      probe(p.substr(0, p.size() - 1), out.p, Tn, C);
+      probe(b.p.substr(0, b.p.size() - 1), out.p, Tn, C);
       return out;
     }
     ln_release(l3);
@@ -1526,25 +1455,22 @@ struct Builder {
     float* h4f = u->keep_intermediates ? alloc((size_t)M * C) : nullptr;
     {
       GemmParams g = gp_base(Tn, M, C); g.seg[0] = seg(gg, 4 * C, Planes{}, 0, 1, 0);
-      g.epi = EPI_RESIDUAL; g.res = h3; g.out = h4f; g.out_hi = h4.hi; g.out_lo = h4.lo; gemm(ops, g, w_ff, 4 * C);
+      g.epi = EPI_RESIDUAL; g.res = h3; g.out = h4f; g.out_hi = h4.hi; g.out_lo = h4.lo; gemm(ops, g, b.w_ff, 4 * C);
     }
     release(gg); release(h3);
-    if (h4f) probe(tb + "ff", h4f, Tn, C);
+    if (h4f) probe(b.tb + "ff", h4f, Tn, C);
 
     Act out{};
     out.p = alloc((size_t)M * C); out.C = C; out.T = Tn; out.Tp = Tp; alloc_stat(out);
     {
       GemmParams g = gp_base(Tn, M, C); g.seg[0] = seg(h4, C, Planes{}, 0, 1, 0);
-      g.epi = EPI_RESIDUAL; g.res = x.p; g.out = out.p; stat_out(g, out);
-      if (want_planes) {
-        Planes pl = alloc_planes((size_t)M * C);
-        out.pl_hi = pl.hi; out.pl_lo = pl.lo; g.out_hi = pl.hi; g.out_lo = pl.lo;
-      }
+      g.epi = EPI_RESIDUAL; g.res = b.x.p; g.out = out.p; stat_out(g, out);
+      if (want_planes) out_planes(g, out);
       offer_next(g, out);
-      gemm(ops, g, w_out, C);
+      gemm(ops, g, b.w_out, C);
     }
     release(h4);
-    probe(p.substr(0, p.size() - 1), out.p, Tn, C);
+    probe(b.p.substr(0, b.p.size() - 1), out.p, Tn, C);
     return out;
   }
 
@@ -1925,10 +1851,8 @@ struct Builder {
       g.w_hi = wo->hi; g.w_lo = wo->lo; g.Kp = wo->Kp; g.N_pad = wo->N_pad; g.bias = wo->bias; g.B = B;
       g.zero_page = u->zero_page;
       const int pr = prec;
-      cur_kind = "gemm"; cur_flops = 2.0 * g.M * (double)co * 3 * C0;
-      cur_desc = "conv_out (NCT store)";
-      if (!dry) u->flops += cur_flops;
-      emit(S, [g, pr, uu](hipStream_t st) { GemmParams gg = g; gg.out = uu->io.y; return launch_gemm(gg, pr, st); });
+      emit_launch(S, "gemm", 2.0 * g.M * (double)co * 3 * C0, "conv_out (NCT store)",
+                  [g, pr, uu](hipStream_t st) { GemmParams gg = g; gg.out = uu->io.y; return launch_gemm(gg, pr, st); });
       if (nf.hi) release(nf);
       release_act(h);
     }
@@ -1979,22 +1903,6 @@ struct Builder {
       u->owned.push_back(z);
       u->zero_page = reinterpret_cast<bf16_t*>(z);
     }
-    const int nblk = H / 32;
-    struct LnIn { Planes pl; float* stat = nullptr; };
-    auto ln_produce = [&](GemmParams& g, float* x32) {   // producer of a k=1 LayerNorm consumer
-      LnIn in;
-      if (!fuse_ln) { (void)x32; return in; }
-      in.pl = alloc_planes((size_t)M * H);
-      in.stat = alloc((size_t)M * nblk * 2);
-      g.out_hi = in.pl.hi; g.out_lo = in.pl.lo; g.rowstat_out = in.stat;
-      return in;
-    };
-    auto ln_consume = [&](GemmParams& g, LnIn& in, const float* x32, const PackedW* w) {
-      if (!fuse_ln) in.pl = ln_apply(S, x32, M, H);
-      else { g.ln_stat = in.stat; g.ln_nblk = nblk; g.ln_u = w->u; g.ln_eps = 1e-5f; }
-      g.seg[0] = seg(in.pl, H, Planes{}, 0, 1, 0);
-    };
-    auto ln_release = [&](LnIn& in) { release(in.pl); if (in.stat) release(in.stat); };
 
     // keep mask of the call -> arena (the GEMM epilogues read it), key bias, masked-LayerNorm'd input planes
     float* keep = alloc((size_t)M);
@@ -2014,7 +1922,7 @@ struct Builder {
     LnIn lin;
     {
       GemmParams g = gp_rows(Ln, M, H); g.seg[0] = seg(p0, cpad, Planes{}, 0, 1, 0);
-      g.out = x; g.rowmask = keep; lin = ln_produce(g, x); gemm(S, g, w_pre, Cin);
+      g.out = x; g.rowmask = keep; lin = ln_produce(g, M, H); gemm(S, g, w_pre, Cin);
     }
     release(p0);
     probe("pre", x, Ln, H);
@@ -2037,7 +1945,7 @@ struct Builder {
       float* qkv = alloc((size_t)M * 3 * H);
       {
         GemmParams g = gp_rows(Ln, M, 3 * H);
-        g.out = qkv; ln_consume(g, lin, x, w_qkv); gemm(S, g, w_qkv, H);
+        g.out = qkv; ln_consume(S, g, lin, x, w_qkv, M, H); gemm(S, g, w_qkv, H);
       }
       ln_release(lin);
       Planes ao = attention(S, qkv, 3 * H, qkv + H, qkv + 2 * H, 3 * H, kbias, Ln, Ln, H);
@@ -2071,7 +1979,7 @@ struct Builder {
       float* x3 = alloc((size_t)M * H);
       {
         GemmParams g = gp_rows(Ln, M, H); g.seg[0] = seg(hh, 4 * H, Planes{}, 0, 1, 0);
-        g.epi = EPI_RESIDUAL; g.res = x2; g.out = x3; g.rowmask = keep; lin = ln_produce(g, x3); gemm(S, g, w_f2, 4 * H);
+        g.epi = EPI_RESIDUAL; g.res = x2; g.out = x3; g.rowmask = keep; lin = ln_produce(g, M, H); gemm(S, g, w_f2, 4 * H);
       }
       release(hh); release(x2);
       x = x3;
@@ -2085,7 +1993,7 @@ struct Builder {
     float* z = alloc((size_t)M * Cout);
     {
       GemmParams g = gp_rows(Ln, M, Cout);
-      g.out = z; g.rowmask = keep; ln_consume(g, lin, x, w_op); gemm(S, g, w_op, H);
+      g.out = z; g.rowmask = keep; ln_consume(S, g, lin, x, w_op, M, H); gemm(S, g, w_op, H);
     }
     ln_release(lin); release(x);
     if (has("layer_norm.weight")) {
