@@ -2582,3 +2582,101 @@ extern "C" int dv_op_attention(const float* q, const float* k, const float* v, c
   if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "attention launch failed: %s (d must be a multiple of 4, <= 64)", hipGetErrorString(e));
   return DV_OK;
 }
+
+// k_attention_frag as the forward runs its cross attention: K | V -> split fragments in the hoisted layout (launch_kv_frag), the
+// key bias as log2-domain rows of whole 32-key tiles (launch_xbias), then launch_attention_frag's own choice of instantiation
+extern "C" int dv_op_attention_frag(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
+                                    int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream) {
+  if (!q || !k || !v || !o || B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return dv_fail(DV_ERR_INVALID, "dv_op_attention_frag: bad argument");
+  if (d <= 0 || d % 16 != 0 || d > 64) return dv_fail(DV_ERR_INVALID, "dv_op_attention_frag: d = %d must be a multiple of 16, <= 64", d);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(attn_init());
+  const int C = H * d, nT = (Tk + 31) / 32, KSq = d / 16, NBv = (d + 31) / 32;
+  const size_t kel = (size_t)B * H * nT * KSq * 64 * 8, vel = (size_t)B * H * nT * 2 * NBv * 64 * 8;
+  OpScratch sc;
+  float* kv = sc.get<float>((size_t)B * Tk * 2 * C * 4, st, false);
+  bf16_t* kf_hi = sc.get<bf16_t>(kel * 2, st, false); bf16_t* kf_lo = sc.get<bf16_t>(kel * 2, st, false);
+  bf16_t* vf_hi = sc.get<bf16_t>(vel * 2, st, false); bf16_t* vf_lo = sc.get<bf16_t>(vel * 2, st, false);
+  float* xb = sc.get<float>((size_t)B * nT * 32 * 4, st, false);
+  if (!kv || !kf_hi || !kf_lo || !vf_hi || !vf_lo || !xb) return dv_fail(DV_ERR_HIP, "dv_op_attention_frag: hipMalloc failed");
+  HIPCHK(hipMemcpy2DAsync(kv, (size_t)2 * C * 4, k, (size_t)C * 4, (size_t)C * 4, (size_t)B * Tk, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpy2DAsync(kv + C, (size_t)2 * C * 4, v, (size_t)C * 4, (size_t)C * 4, (size_t)B * Tk, hipMemcpyDeviceToDevice, st));
+  HIPCHK(launch_kv_frag(kv, kf_hi, kf_lo, vf_hi, vf_lo, B, Tk, C, H, st));
+  HIPCHK(launch_xbias(bias, xb, B, Tk, nT, st));
+  AttnFragParams a{};
+  a.q = q; a.ldq = C;
+  a.kf_hi = kf_hi; a.kf_lo = kf_lo; a.vf_hi = vf_hi; a.vf_lo = vf_lo;
+  a.k_b = H * nT * KSq; a.k_h = nT * KSq; a.k_t = KSq;
+  a.v_b = H * nT * 2 * NBv; a.v_h = nT * 2 * NBv; a.v_t = 2 * NBv; a.v_kb = NBv; a.v_nb = 1; a.self_layout = 0;
+  a.bias = xb; a.bias_ld = nT * 32;
+  a.o = o; a.o_hi = nullptr; a.o_lo = nullptr; a.ldo = C;
+  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.d = d; a.scale = 1.0f / sqrtf((float)d); a.nsplit = 3;
+  hipError_t e = launch_attention_frag(a, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_attention_frag: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
+// The k = 3 convolutions of ResnetBlock2D / Upsample2D as the forward launches them: split planes of a channels-last input in a
+// (padded) row space, packed weights AND their fragment-major copies, through launch_gemm - which then routes to k_conv3 /
+// k_conv3s / k_conv3u.  A shape launch_gemm would hand to k_gemm is refused.
+extern "C" int dv_op_conv3(const float* x, const float* w, const float* bias, const float* x_sc, const float* w_sc, float* y, int32_t B,
+                           int32_t Cin, int32_t T, int32_t Tp, int32_t Cout, int32_t Csc, int32_t up2, void* stream) {
+  if (!x || !w || !y || B <= 0 || Cin <= 0 || T <= 0 || Tp < T || Cout <= 0 || Csc < 0 || (Csc > 0 && (!x_sc || !w_sc || up2)))
+    return dv_fail(DV_ERR_INVALID, "dv_op_conv3: bad argument");
+  if (Cin % 64 != 0 || Csc % 64 != 0 || 2 * (size_t)std::max(Cin, Csc) + 256 > DV_ZERO_PAGE_BYTES)
+    return dv_fail(DV_ERR_INVALID, "dv_op_conv3: Cin = %d / Csc = %d must be multiples of 64 within one source tensor's width", Cin, Csc);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(gemm_init());
+  gemm_env_refresh();
+  HIPCHK(attn_init());
+  const int Kp = 3 * Cin + Csc, Npad = rup(Cout, 128);
+  const int Tv_out = up2 ? 2 * T : T, T_out = up2 ? rup(2 * T, 32) : Tp;
+  GemmParams g{};
+  g.nseg = Csc > 0 ? 2 : 1; g.B = B;
+  g.T_in = Tp; g.Tv_in = T; g.T_out = T_out; g.Tv_out = g.T_virt = Tv_out;
+  g.stride = 1; g.up_mode = up2 ? UP_X2 : UP_NONE;
+  g.M = B * T_out; g.N = Cout; g.epi = EPI_STORE; g.ldo = Cout; g.ldres = Cout; g.Kp = Kp; g.N_pad = Npad; g.bias = bias;
+  g.seg[0].c0 = Cin; g.seg[0].taps = 3; g.seg[0].pad = 1;
+  if (Csc > 0) { g.seg[1].c0 = Csc; g.seg[1].taps = 1; g.seg[1].pad = 0; }
+  const int route = gemm_conv3_up_ok(g) ? 2 : ((gemm_conv3_shape_ok(g) && Kp == gemm_conv3_k(g)) ? 1 : 0);
+  if (route == 0)
+    return dv_fail(DV_ERR_INVALID, "dv_op_conv3: B=%d Cin=%d T=%d Tp=%d Cout=%d Csc=%d up2=%d is not a shape of the convolution kernels "
+                   "(it would run on k_gemm)", B, Cin, T, Tp, Cout, Csc, up2);
+  OpScratch sc;
+  const size_t xe = (size_t)B * Tp * Cin, se = (size_t)B * Tp * Csc, we = (size_t)Npad * Kp;
+  bf16_t* xh = sc.get<bf16_t>(xe * 2, st, false); bf16_t* xl = sc.get<bf16_t>(xe * 2, st, false);
+  bf16_t* sh = Csc > 0 ? sc.get<bf16_t>(se * 2, st, false) : nullptr; bf16_t* sl = Csc > 0 ? sc.get<bf16_t>(se * 2, st, false) : nullptr;
+  bf16_t* hi = sc.get<bf16_t>(we * 2, st, true); bf16_t* lo = sc.get<bf16_t>(we * 2, st, true);
+  bf16_t* fhi = sc.get<bf16_t>(we * 2, st, false); bf16_t* flo = sc.get<bf16_t>(we * 2, st, false);
+  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
+  if (!xh || !xl || !hi || !lo || !fhi || !flo || !zp || (Csc > 0 && (!sh || !sl))) return dv_fail(DV_ERR_HIP, "dv_op_conv3: hipMalloc failed");
+  HIPCHK(launch_split(x, xh, xl, (int64_t)xe, st));
+  if (Csc > 0) HIPCHK(launch_split(x_sc, sh, sl, (int64_t)se, st));
+  PackSpec s{};
+  s.src = w; s.N = Cout; s.kind = 1; s.C = Cin; s.taps = 3; s.c_pad = Cin; s.k_off = 0; s.n_off = 0;
+  HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
+  if (Csc > 0) {
+    s.src = w_sc; s.C = Csc; s.taps = 1; s.c_pad = Csc; s.k_off = 3 * Cin;
+    HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
+  }
+  HIPCHK(launch_relayout_frag(hi, fhi, Npad, Kp, st));
+  HIPCHK(launch_relayout_frag(lo, flo, Npad, Kp, st));
+  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl;
+  if (Csc > 0) { g.seg[1].a0_hi = sh; g.seg[1].a0_lo = sl; }
+  g.w_hi = hi; g.w_lo = lo; g.wf_hi = fhi; g.wf_lo = flo; g.out = y; g.zero_page = zp;
+  if (route == 1) {   // the 128-frame level's long-K convolutions run as a fused split-K pair on the streaming kernel: here too
+    int dev = 0, n_cu = 0;
+    (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (gemm_conv3_split(g, n_cu) == 2 && ((g.M + 31) / 32) * ((g.N + 31) / 32) <= 4096) {
+      g.sk_split = 2;
+      g.sk_buf = sc.get<float>(gemm_conv3_split_bytes(g), st, false);
+      g.sk_ticket = sc.get<unsigned>(4096 * sizeof(unsigned), st, true);
+      if (!g.sk_buf || !g.sk_ticket) return dv_fail(DV_ERR_HIP, "dv_op_conv3: hipMalloc failed");
+    }
+  }
+  hipError_t e = launch_gemm(g, DV_PREC_BF16X3, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_conv3: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}

@@ -293,6 +293,22 @@ int dv_op_group_stats(const float* x, float* mean, float* rstd, int32_t B, int32
  * axis as the reference's .view(B,-1,H,d)); bias [B, Tk] additive or NULL. */
 int dv_op_attention(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
                     int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream);
+/* The same operation on the kernel the forward runs (k_attention_frag): k | v become split-bf16 MFMA fragments of 32-key tiles
+ * in the layout of the hoisted cross-attention keys / values, bias [B, Tk] (or NULL) becomes log2-domain rows of whole tiles,
+ * and the launcher picks its instantiation (waves per workgroup, key split) from the shape as it does in the forward.  d must
+ * be a multiple of 16, <= 64. */
+int dv_op_attention_frag(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
+                         int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream);
+/* The k = 3, padding 1 convolution of ResnetBlock2D / Upsample2D on the kernels the forward runs it on (k_conv3: Cin <= 512;
+ * k_conv3s: wider, or with the folded 1x1 shortcut; k_conv3u: up2), on CHANNELS-LAST tensors in a padded row space:
+ *   x [B, Tp, Cin], w [Cout, Cin, 3], bias [Cout] or NULL;  T frames of every utterance exist, Tp >= T is the row pitch (a
+ *   multiple of 32, T > Tp - 32); rows [T, Tp) of x may hold anything finite and reach no output frame.
+ *   Csc > 0: + the 1x1 convolution w_sc [Cout, Csc, 1] of x_sc [B, Tp, Csc] as a second K segment (bias = the sum of both).
+ *   up2 = 0: y [B, Tp, Cout].  up2 = 1: nearest x2 upsampling first, y [B, Tpo, Cout] with 2 T frames, Tpo = 2 T rounded up to 32.
+ * Cin a multiple of 128 (128 .. 1024; up2: 128 .. 512), Cout a multiple of 64.  A shape that would run on the general GEMM
+ * kernel is an error (-1), never a silent fall-back. */
+int dv_op_conv3(const float* x, const float* w, const float* bias, const float* x_sc, const float* w_sc, float* y, int32_t B,
+                int32_t Cin, int32_t T, int32_t Tp, int32_t Cout, int32_t Csc, int32_t up2, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from parity_metrics import frame_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -193,3 +194,176 @@ def test_attention(B, H, Tq, Tk, d, masked):
     # reference output (profiles/r04_err_vs_goldens_p_fp16.txt; budget 1e-3).  DV_ATTN_PF16=0 builds restore the old form.
     err = rel_l2(o.cpu().numpy(), ref.numpy())
     assert err < 3e-4, err
+
+
+# ----------------------------------------------------------------------------- the kernels the forward really launches
+def _frag_instantiation(B, H, Tq, Tk, d):
+    """(d, waves per workgroup, key split) launch_attention_frag picks (csrc/kernels_attn.hip): 8 waves from 1100 (utterance, head,
+    32-query block) jobs, 4 from 64, else 2; the keys split over two half-workgroups when there are at most 160 plain workgroups
+    and more than 64 keys."""
+    waves = B * H * -(-Tq // 32)
+    nw = 8 if waves >= 1100 else (4 if waves >= 64 else 2)
+    plain = -(-Tq // (32 * nw)) * H * B
+    return d, nw, 2 if (nw >= 4 and plain <= 160 and Tk > 64) else 1
+
+
+# (B, H, Tq, Tk, d, mask, logit scale).  mask: None; "ragged" (the last 7 (b + 1) keys off); "one" (a single valid key);
+# "all" (utterance 0 fully masked: -10000 on every key = plain attention over all keys, SURVEY quirk 2; the others ragged);
+# "tile" (the valid keys end exactly on a 32-key tile boundary)
+ATTN_FRAG_SHAPES = [
+    (1, 8, 1, 1, 16, None, 1), (2, 8, 31, 31, 16, "ragged", 1), (2, 8, 33, 32, 32, None, 1), (1, 8, 300, 33, 16, "one", 1),
+    (2, 8, 100, 64, 48, "tile", 1), (2, 8, 300, 65, 16, "ragged", 1), (1, 8, 96, 97, 64, "all", 1), (2, 8, 512, 161, 64, None, 8),
+    (2, 8, 300, 97, 32, "all", 1), (2, 8, 300, 161, 48, "tile", 1), (2, 8, 300, 128, 64, "one", 8),     # 4 waves, keys split
+    (2, 8, 1500, 77, 16, "ragged", 1), (2, 8, 1500, 256, 32, None, 1), (2, 8, 300, 64, 48, "ragged", 1),
+    (2, 8, 1500, 100, 64, "all", 1),                                                                      # 4 waves, plain
+    (1, 8, 64, 300, 16, "tile", 1), (1, 4, 33, 65, 32, "ragged", 8), (1, 8, 31, 161, 48, None, 1), (1, 2, 300, 97, 64, "ragged", 1),   # 2 waves
+    (2, 8, 3000, 97, 16, "ragged", 1), (2, 8, 3000, 33, 32, "one", 1), (2, 8, 3000, 65, 48, None, 1), (2, 8, 3000, 256, 64, "tile", 1),  # 8 waves, plain
+    (1, 8, 4416, 97, 16, None, 1), (1, 8, 4416, 65, 32, "all", 1), (1, 8, 4416, 161, 48, "ragged", 1), (1, 8, 4416, 128, 64, "ragged", 8),  # 8 waves, keys split
+]
+
+
+def test_attention_frag_shapes_cover_every_instantiation():
+    want = {(d, nw, ks) for d in (16, 32, 48, 64) for nw, ks in ((8, 1), (4, 1), (2, 1), (8, 2), (4, 2))}
+    have = {_frag_instantiation(B, H, Tq, Tk, d) for B, H, Tq, Tk, d, _, _ in ATTN_FRAG_SHAPES}
+    assert len(want) == 20 and have == want, sorted(want ^ have)
+    assert {1, 31, 32, 33, 64, 65, 97, 161} <= {s[3] for s in ATTN_FRAG_SHAPES}
+    assert {1, 31, 33, 300} <= {s[2] for s in ATTN_FRAG_SHAPES}
+    assert {None, "ragged", "one", "all", "tile"} == {s[5] for s in ATTN_FRAG_SHAPES} and any(s[6] == 8 for s in ATTN_FRAG_SHAPES)
+
+
+@pytest.mark.parametrize("B,H,Tq,Tk,d,mask,qs", ATTN_FRAG_SHAPES)
+def test_attention_frag(B, H, Tq, Tk, d, mask, qs):
+    """k_attention_frag (every instantiation: d x waves per workgroup x key split) over fragments made by k_kv_frag, as the
+    forward runs its cross attention, against fp64 scaled_dot_product_attention.  Whole tensor: 3e-4, test_attention's bound
+    (one fp16 plane of P: rms 2^-12 / sqrt 3 = 1.4e-4).  Per query row: 2 x the worst row of a host emulation of that arithmetic
+    on the same inputs - fp64 attention whose logits are formed in fp32 as the reference forms them (q k^T d^-1/2 + mask in
+    float32: a -10000 mask costs the logit 10 bits) and whose probabilities exp(s - max) are rounded to fp16 before P V; the
+    factor 2 is the split-bf16 operands' share, and 2^-16 is added for what two bf16 planes can hold of an operand at all (16
+    significand bits: with a single valid key the emulation is exact and the bound would be zero).  Bit-equal with itself
+    across two calls."""
+    L = _lib()
+    q = _synth("q", (B, Tq, H * d), float(qs))
+    k, v = _synth("k", (B, Tk, H * d)), _synth("v", (B, Tk, H * d))
+    bias = None
+    if mask is not None:
+        bias = np.zeros((B, Tk), dtype=np.float32)
+        for b in range(B):
+            if mask == "ragged":
+                bias[b, max(1, Tk - 7 * (b + 1)):] = -10000.0
+            elif mask == "one":
+                bias[b] = -10000.0
+                bias[b, (5 * b + 3) % Tk] = 0.0
+            elif mask == "all":
+                bias[b, (0 if b == 0 else max(1, Tk - 9)):] = -10000.0
+            elif mask == "tile":
+                bias[b, max(1, (Tk - 1) // 32 * 32 - 32 * b):] = -10000.0
+    tq = torch.from_numpy(q).view(B, Tq, H, d).transpose(1, 2).double()
+    tk = torch.from_numpy(k).view(B, Tk, H, d).transpose(1, 2).double()
+    tv = torch.from_numpy(v).view(B, Tk, H, d).transpose(1, 2).double()
+    am = None if bias is None else torch.from_numpy(bias)[:, None, None, :].expand(B, H, 1, Tk).double()
+    ref = F.scaled_dot_product_attention(tq, tk, tv, attn_mask=am).transpose(1, 2).reshape(B, Tq, H * d)
+    # the host emulation (reference-side arithmetic only)
+    s = (tq @ tk.transpose(-1, -2) / np.sqrt(d)).float()
+    if am is not None:
+        s = s + am.float()
+    s = s.double()
+    p = torch.exp(s - s.amax(-1, keepdim=True))
+    emu = ((p.half().double() @ tv) / p.sum(-1, keepdim=True)).transpose(1, 2).reshape(B, Tq, H * d)
+    row_bound = 2.0 * frame_errors(emu, ref)["worst"] + 2.0 ** -16
+
+    dq, dk, dv = _dev(q), _dev(k), _dev(v)
+    dbias = None if bias is None else _dev(bias)
+    outs = []
+    for _ in range(2):
+        o = torch.full((B, Tq, H * d), float("nan"), device="cuda")
+        L.check(L.lib().dv_op_attention_frag(L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(dbias), L.ptr(o), B, H, Tq, Tk, d, None),
+                "dv_op_attention_frag")
+        torch.cuda.synchronize()
+        outs.append(o.cpu())
+    assert torch.equal(outs[0], outs[1])
+    fe = frame_errors(outs[0], ref)
+    print("attention_frag %s: tensor %.3e, worst row %.3e at %s, row bound %.3e" % (_frag_instantiation(B, H, Tq, Tk, d), fe["rel_l2"],
+                                                                                   fe["worst"], fe["at"], row_bound))
+    assert fe["rel_l2"] < 3e-4, fe["rel_l2"]
+    assert fe["worst"] < row_bound, (fe["worst"], row_bound, fe["at"])
+
+
+def test_attention_frag_refuses_other_head_dims():
+    L = _lib()
+    z = torch.zeros(2 * 40 * 8 * 12, device="cuda")
+    assert L.lib().dv_op_attention_frag(L.ptr(z), L.ptr(z), L.ptr(z), None, L.ptr(z), 2, 8, 40, 40, 12, None) == -1
+    assert b"multiple of 16" in L.lib().dv_last_error()
+
+
+CONV3_SHAPES = [
+    # (B, Cin, T, Tp, Cout, Csc, up2)
+    (2, 128, 64, 64, 128, 0, 0), (2, 256, 63, 64, 256, 0, 0), (2, 384, 65, 96, 384, 0, 0), (2, 512, 100, 128, 512, 0, 0),   # k_conv3<CIN>
+    (3, 128, 300, 320, 256, 0, 0), (8, 128, 1024, 1024, 128, 0, 0), (2, 512, 1024, 1024, 192, 0, 0),
+    (2, 640, 100, 128, 256, 0, 0), (2, 768, 64, 64, 384, 0, 0), (2, 896, 63, 64, 384, 0, 0), (1, 1024, 65, 96, 512, 0, 0),   # k_conv3s: the up path's concatenations
+    (8, 1024, 128, 128, 512, 0, 0),                                                                                       # ... as a fused split-K pair
+    (2, 128, 100, 128, 128, 256, 0), (2, 256, 300, 320, 256, 384, 0), (4, 512, 128, 128, 512, 1024, 0), (3, 384, 65, 96, 320, 640, 0),  # + the folded 1x1 shortcut
+    (2, 128, 64, 64, 128, 0, 1), (2, 256, 50, 64, 256, 0, 1), (3, 384, 75, 96, 384, 0, 1), (2, 512, 32, 32, 512, 0, 1),       # k_conv3u
+    (8, 256, 512, 512, 256, 0, 1),
+]
+
+
+@pytest.mark.parametrize("B,Cin,T,Tp,Cout,Csc,up2", CONV3_SHAPES)
+def test_conv3(B, Cin, T, Tp, Cout, Csc, up2):
+    """The three-tap convolution through the fragment-major weights - the route of the forward to k_conv3<128 | 256 | 384 | 512>,
+    k_conv3s (wider inputs, or the folded 1x1 shortcut as a second K segment; also as a fused split-K pair) and k_conv3u (nearest
+    x2 upsampling) - against fp64 conv1d on the frames that exist.  The padding rows [T, Tp) of the inputs hold large finite
+    garbage, which must reach no output frame.  Whole tensor 1e-4 (test_conv1d's bound for the same split-bf16 contraction), and
+    the same 1e-4 on EVERY frame; the first frame, the last frame and the frames at the 64-row tile seams are reported apart."""
+    L = _lib()
+    rng = np.random.default_rng(7)
+
+    def padded(name, C):
+        a = np.empty((B, Tp, C), dtype=np.float32)
+        a[:, :T] = _synth(name, (B, T, C))
+        a[:, T:] = (3.0e4 * rng.standard_normal((B, Tp - T, C))).astype(np.float32)
+        return a
+
+    x = padded("x", Cin)
+    w = _synth("w", (Cout, Cin, 3), 1.0 / np.sqrt(Cin * 3))
+    b = _synth("b", (Cout,), 0.1)
+    xt = torch.from_numpy(x[:, :T]).double().permute(0, 2, 1)
+    if up2:
+        xt = F.interpolate(xt, scale_factor=2, mode="nearest")
+    ref = F.conv1d(xt, torch.from_numpy(w).double(), torch.from_numpy(b).double(), padding=1)
+    dxs = dws = None
+    if Csc:
+        xs = padded("xs", Csc)
+        ws = _synth("ws", (Cout, Csc, 1), 1.0 / np.sqrt(Csc))
+        ref = ref + F.conv1d(torch.from_numpy(xs[:, :T]).double().permute(0, 2, 1), torch.from_numpy(ws).double())
+        dxs, dws = _dev(xs), _dev(ws)
+    ref = ref.permute(0, 2, 1).contiguous()                           # [B, T_out, Cout]
+    To = 2 * T if up2 else T
+    Tpo = (2 * T + 31) // 32 * 32 if up2 else Tp
+    y = torch.full((B, Tpo, Cout), float("nan"), device="cuda")
+    dx, dw, db = _dev(x), _dev(w), _dev(b)
+    L.check(L.lib().dv_op_conv3(L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(dxs), L.ptr(dws), L.ptr(y), B, Cin, T, Tp, Cout, Csc, up2, None),
+            "dv_op_conv3")
+    torch.cuda.synchronize()
+    got = y.cpu()[:, :To]
+    assert torch.isfinite(got).all()
+    fe = frame_errors(got, ref)
+    per = fe["per_frame"]
+    tile = 128 if up2 else 64
+    seams = sorted({t for t in range(To) if t % tile in (0, tile - 1)} - {0, To - 1})
+    inner = sorted(set(range(To)) - set(seams) - {0, To - 1})
+    msg = "tensor %.2e; first frame %.2e, last frame %.2e, tile seams %.2e, other frames %.2e; worst %.2e at %s" % (
+        fe["rel_l2"], per[:, 0].max(), per[:, To - 1].max(), per[:, seams].max() if seams else 0.0,
+        per[:, inner].max() if inner else 0.0, fe["worst"], fe["at"])
+    print("conv3", (B, Cin, T, Tp, Cout, Csc, up2), msg)
+    assert fe["floored_ok"], (fe["floored"], fe["frames"])
+    assert fe["rel_l2"] < 1e-4, msg
+    assert fe["worst"] < 1e-4, msg
+
+
+def test_conv3_refuses_what_would_run_on_the_general_gemm():
+    L = _lib()
+    z = torch.zeros(1 << 20, device="cuda")
+    for B, Cin, T, Tp, Cout, Csc, up2 in [(2, 192, 64, 64, 128, 0, 0), (2, 128, 60, 128, 128, 0, 0), (2, 128, 64, 64, 96, 0, 0),
+                                          (2, 640, 64, 64, 128, 0, 1)]:
+        rc = L.lib().dv_op_conv3(L.ptr(z), L.ptr(z), None, None, None, L.ptr(z), B, Cin, T, Tp, Cout, Csc, up2, None)
+        assert rc == -1 and b"k_gemm" in L.lib().dv_last_error(), (B, Cin, T, Tp, Cout, Csc, up2)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import UNET_CASES, oracle_cfg, rel_l2, unet_case
+from parity_metrics import frame_errors, oracle_probes as _oracle_probes
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +23,11 @@ def _build(name, precision="bf16x3"):
     m = m.cuda()
     m.hip_engine(precision)
     return m, kw, sd, sample, t, enc, mask
+
+
+def _frames(y, ref):
+    """parity_metrics.frame_errors of channels-first [B, C, T] outputs"""
+    return frame_errors(np.ascontiguousarray(np.transpose(y, (0, 2, 1))), np.ascontiguousarray(np.transpose(ref, (0, 2, 1))))
 
 
 def _mask_arg(name, mask):
@@ -37,69 +43,6 @@ PROBES_TINY = ["emb", "conv_in", "down_blocks.0.resnets.0.conv1", "down_blocks.0
                "down_blocks.3.resnets.1", "mid_block.resnets.0", "mid_block.attentions.0", "mid_block.resnets.1",
                "up_blocks.0.resnets.0", "up_blocks.0.upsamplers.0", "up_blocks.1.resnets.0", "up_blocks.1.attentions.2",
                "up_blocks.3.attentions.2"]
-
-
-def _oracle_probes(kw, sd, sample, t, enc, mask_t):
-    """Named intermediates of the oracle, keyed like the engine's probes (channels-last)."""
-    import torch.nn.functional as F
-    from oracle import unet_ref as R
-    out = {}
-    orig = {n: getattr(R, n) for n in ("resnet_block", "transformer_1d", "downsample", "upsample", "transformer_block",
-                                       "attention")}
-
-    def tap(name, v):
-        out[name] = v.permute(0, 2, 1).contiguous() if v.dim() == 3 else v
-
-    def resnet_block(sdd, p, cfg, x, emb):
-        g, eps = cfg["norm_num_groups"], cfg["norm_eps"]
-        h = F.conv1d(F.silu(F.group_norm(x, g, sdd[p + "norm1.weight"], sdd[p + "norm1.bias"], eps)),
-                     sdd[p + "conv1.weight"], sdd[p + "conv1.bias"], padding=1)
-        tap(p + "conv1", h)
-        y = orig["resnet_block"](sdd, p, cfg, x, emb)
-        tap(p[:-1], y)
-        return y
-
-    def transformer_1d(sdd, p, cfg, x, e, b):
-        h = F.group_norm(x, cfg["norm_num_groups"], sdd[p + "norm.weight"], sdd[p + "norm.bias"], 1e-6)
-        h = F.conv1d(h, sdd[p + "proj_in.weight"], sdd[p + "proj_in.bias"])
-        tap(p + "proj_in", h)
-        y = orig["transformer_1d"](sdd, p, cfg, x, e, b)
-        tap(p[:-1], y)
-        return y
-
-    def transformer_block(sdd, p, heads, x, e, b):
-        C = x.shape[-1]
-        n = F.layer_norm(x, (C,), sdd[p + "norm1.weight"], sdd[p + "norm1.bias"], 1e-5)
-        x1 = orig["attention"](sdd, p + "attn1.", heads, n) + x
-        out[p + "attn1"] = x1
-        n = F.layer_norm(x1, (C,), sdd[p + "norm2.weight"], sdd[p + "norm2.bias"], 1e-5)
-        x2 = orig["attention"](sdd, p + "attn2.", heads, n, e, b) + x1
-        out[p + "attn2"] = x2
-        y = orig["transformer_block"](sdd, p, heads, x, e, b)
-        out[p + "ff"] = y
-        return y
-
-    def downsample(sdd, p, x):
-        y = orig["downsample"](sdd, p, x)
-        tap(p[:-1], y)
-        return y
-
-    def upsample(sdd, p, x, size=None):
-        y = orig["upsample"](sdd, p, x, size)
-        tap(p[:-1], y)
-        return y
-
-    R.resnet_block, R.transformer_1d, R.transformer_block, R.downsample, R.upsample = (
-        resnet_block, transformer_1d, transformer_block, downsample, upsample)
-    try:
-        pr = {}
-        y = R.unet_forward(sd, oracle_cfg(kw), sample, t, enc, mask_t, probes=pr)
-    finally:
-        for n, f in orig.items():
-            setattr(R, n, f)
-    out["emb"] = pr["emb"][:, None, :]
-    tap("conv_in", pr["conv_in"])
-    return y, out
 
 
 def test_unet_tiny_layerwise():
@@ -137,6 +80,8 @@ def test_unet_vs_golden(name, gold):
               encoder_attention_mask=_mask_arg(name, mask).cuda()).sample
     err = rel_l2(y.cpu().numpy(), gold("unet_%s.npz" % name)["y"])
     assert err < 2e-4, err
+    fe = _frames(y.cpu().numpy(), gold("unet_%s.npz" % name)["y"])       # ... and every frame within the budget of the header
+    assert fe["worst"] < 1e-3, (fe["worst"], fe["at"])
 
 
 def test_unet_cfg1_golden_on_the_convolution_kernels(gold):
@@ -267,6 +212,9 @@ def test_odd_lengths_run_the_fused_schedule_and_match_the_oracle(B, T, L):
     assert np.isfinite(outs[0]).all()
     assert rel_l2(outs[0], y_ref) < 2e-4, rel_l2(outs[0], y_ref)
     assert rel_l2(outs[1], y_ref) < 2e-4
+    for o in outs:
+        fe = _frames(o, y_ref)
+        assert fe["worst"] < 1e-3, (fe["worst"], fe["at"])
     assert rel_l2(outs[0], outs[1]) < 5e-5
     # (<= 156 launches, + 10 per level that has fewer than 128 rows in the whole batch and so runs one launch per GEMM instead of
     # the row-block chains - engine.hip chain_min_rows; B = 2, T = 37: levels of 64 / 64 / 64 / 64 rows)
@@ -426,6 +374,8 @@ def test_config2_full_size_forward_vs_oracle():
                                     torch.from_numpy(enc), torch.from_numpy(mask))
     err = rel_l2(y.cpu().numpy(), ref.numpy())
     assert err < 2e-4, err
+    fe = _frames(y.cpu().numpy(), ref.numpy())
+    assert fe["worst"] < 1e-3, (fe["worst"], fe["at"])
 
 
 def test_config2_full_size_sampler_steps_vs_oracle():
