@@ -18,6 +18,7 @@
 
 #include <array>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -737,6 +738,8 @@ static int run_events(dv_plan* p, float* x, int64_t numel, EvalFn eval, hipStrea
 
 extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const float* cond, void* stream) {
   if (!p || !u || !x_inout) return dv_fail(DV_ERR_INVALID, "dv_sampler_run: null argument");
+  if ((uintptr_t)x_inout % 16 != 0)   // k_lincomb reads and writes x as float4
+    return dv_fail(DV_ERR_INVALID, "dv_sampler_run: x_inout (%p) must be 16-byte aligned", (void*)x_inout);
   int B, T, cin, cout; int64_t gen;
   if (!dv_unet_dims(u, &B, &T, &cin, &cout, &gen)) return dv_fail(DV_ERR_STATE, "dv_sampler_run: unet not prepared / cond not set");
   if (cin > cout && !cond) return dv_fail(DV_ERR_INVALID, "dv_sampler_run: cond is required (in_channels > out_channels)");
@@ -785,6 +788,8 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
 
 extern "C" int dv_sampler_run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int64_t numel, void* stream) {
   if (!p || !fn || !x_inout || numel <= 0) return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: bad argument");
+  if ((uintptr_t)x_inout % 16 != 0)   // k_lincomb reads and writes x as float4
+    return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: x_inout (%p) must be 16-byte aligned", (void*)x_inout);
   int rc = plan_buffers(p, numel, 0);
   if (rc != DV_OK) return rc;
   hipStream_t st = (hipStream_t)stream;

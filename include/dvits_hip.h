@@ -242,11 +242,13 @@ int dv_plan_events(const dv_plan* p, int32_t* n_events, int32_t* ev9, int32_t* n
 /* Run the whole loop: x_inout [B, C, T] is x_T on entry and x_0 on exit; cond
  * [B, in_channels-C, T] is the channel-concat condition.  dv_unet_set_cond must have been
  * called.  The first call for a given (plan, unet shape) captures the loop into a
- * hipGraph; later calls replay it. */
+ * hipGraph; later calls replay it.  x_inout must be 16-byte aligned (the update kernel moves it as float4):
+ * DV_ERR_INVALID otherwise, before anything is launched. */
 int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const float* cond, void* stream);
 
 /* Same loop with a caller-supplied model instead of the UNet, for sampler known-answer
- * tests: model(user, x_dev, t_input_host, out_dev) must enqueue out = f(x, t) on `stream`. */
+ * tests: model(user, x_dev, t_input_host, out_dev) must enqueue out = f(x, t) on `stream`.  x_inout [numel], any
+ * numel >= 1, 16-byte aligned like dv_sampler_run's (DV_ERR_INVALID otherwise, before anything is launched). */
 typedef int (*dv_model_fn)(void* user, const float* x, double t_input, float* out, void* stream);
 int dv_sampler_run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int64_t numel, void* stream);
 
