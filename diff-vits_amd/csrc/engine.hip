@@ -154,7 +154,9 @@ struct Act {   // channels-last fp32 [B*Tp, C] (+ GN statistics) (+ split planes
 
 typedef std::function<hipError_t(hipStream_t)> OpFn;
 
-struct Probe { std::string name; float* p; int T, C, Tp; };
+// p: fp32 rows, Tp frames per utterance apart.  Split-plane tensors (p null): hi (+ lo, bf16x3) planes, joined on the host and
+// multiplied by `scale` (a factor the schedule folds into the consumer's weights)
+struct Probe { std::string name; float* p; int T, C, Tp; const bf16_t* hi = nullptr; const bf16_t* lo = nullptr; float scale = 1.f; };
 
 struct dv_unet {
   dv_unet_cfg cfg{};
@@ -447,6 +449,11 @@ struct Builder {
   }
   void probe(const std::string& name, const float* p, int T_, int C_) {
     if (!dry && u->keep_intermediates) u->probes.push_back(Probe{name, const_cast<float*>(p), T_, C_, T_ > 1 ? pitch(T_) : T_});
+  }
+  // the prompt encoder's tensors are [B * L, C] with no row padding, whatever pitch() says of L (with n_levels = 0
+  // stat16_everywhere() holds vacuously and pitch(L) would be rup(L, 32))
+  void probe_rows(const std::string& name, const float* p, int T_, int C_) {
+    if (!dry && u->keep_intermediates) u->probes.push_back(Probe{name, const_cast<float*>(p), T_, C_, T_});
   }
 
   // ---- weight packing (only in the real pass; device work on pack_stream)
@@ -1925,7 +1932,7 @@ struct Builder {
       g.out = x; g.rowmask = keep; lin = ln_produce(g, M, H); gemm(S, g, w_pre, Cin);
     }
     release(p0);
-    probe("pre", x, Ln, H);
+    probe_rows("pre", x, Ln, H);
 
     const_vec("__const.ffn_scale", 4 * H, 1.0f / sqrtf((float)KS9));
     for (int i = 0; i < c.n_layers; ++i) {
@@ -1956,6 +1963,7 @@ struct Builder {
         g.epi = EPI_RESIDUAL; g.res = x; g.out = x2; g.rowmask = keep; gemm(S, g, w_o, H);
       }
       release(ao); release(x);
+      probe_rows("layer" + std::to_string(i) + ".attn", x2, Ln, H);
 
       // feed-forward: LayerNorm2 WITH affine (the k=9 zero padding pads the normalised tensor), then the nine
       // shifted Linears as one contraction over two K-segments of the same planes: tap 0 at offset 0 (the
@@ -1976,6 +1984,9 @@ struct Builder {
         gemm(S, g, w_f1, KS9 * H);
       }
       release(n2);
+      // (the planes hold relu(a); the reference's relu(k^-1/2 a) is that times the scale ffn_2's weights carry)
+      if (!dry && u->keep_intermediates)
+        u->probes.push_back(Probe{"layer" + std::to_string(i) + ".ffn1", nullptr, Ln, 4 * H, Ln, hh.hi, hh.lo, 1.0f / sqrtf((float)KS9)});
       float* x3 = alloc((size_t)M * H);
       {
         GemmParams g = gp_rows(Ln, M, H); g.seg[0] = seg(hh, 4 * H, Planes{}, 0, 1, 0);
@@ -1983,7 +1994,7 @@ struct Builder {
       }
       release(hh); release(x2);
       x = x3;
-      probe("layer" + std::to_string(i), x, Ln, H);
+      probe_rows("layer" + std::to_string(i), x, Ln, H);
     }
 
     // out_proj ConvLayer (no masked_fill: model3.py:427), then the last LayerNorm with affine, both re-masked
@@ -1996,6 +2007,7 @@ struct Builder {
       g.out = z; g.rowmask = keep; ln_consume(S, g, lin, x, w_op, M, H); gemm(S, g, w_op, H);
     }
     ln_release(lin); release(x);
+    probe_rows("out_proj", z, Ln, Cout);
     if (has("layer_norm.weight")) {
       const float* gl = W("layer_norm.weight"); const float* bl = W("layer_norm.bias");
       cur_kind = "ln_apply";
@@ -2436,8 +2448,7 @@ int dv_unet_dims(const dv_unet* u, int* B, int* T, int* cin, int* cout, int64_t*
   return u->prepared && u->cond_set;
 }
 
-extern "C" int dv_unet_probe(dv_unet* u, const char* name, float* host_out, int64_t capacity, int64_t* dims) {
-  if (!u || !name) return dv_fail(DV_ERR_INVALID, "dv_unet_probe: null argument");
+static int probe_copy(dv_unet* u, const char* name, float* host_out, int64_t capacity, int64_t* dims) {
   for (const Probe& p : u->probes) {
     if (p.name == name) {
       const int64_t n = (int64_t)u->B * p.T * p.C;
@@ -2445,6 +2456,14 @@ extern "C" int dv_unet_probe(dv_unet* u, const char* name, float* host_out, int6
       if (!host_out) return DV_OK;
       if (capacity < n) return dv_fail(DV_ERR_INVALID, "probe buffer too small");
       HIPCHK(hipDeviceSynchronize());
+      if (!p.p) {   // split planes, unpadded rows: fp32 value = hi + lo (bf16 bits are the upper half of an fp32)
+        std::vector<bf16_t> h((size_t)n), l;
+        HIPCHK(hipMemcpy(h.data(), p.hi, (size_t)n * sizeof(bf16_t), hipMemcpyDeviceToHost));
+        if (p.lo) { l.resize((size_t)n); HIPCHK(hipMemcpy(l.data(), p.lo, (size_t)n * sizeof(bf16_t), hipMemcpyDeviceToHost)); }
+        auto f32 = [](bf16_t b) { const uint32_t w = (uint32_t)b << 16; float f; memcpy(&f, &w, 4); return f; };
+        for (int64_t i = 0; i < n; ++i) host_out[i] = p.scale * (f32(h[(size_t)i]) + (p.lo ? f32(l[(size_t)i]) : 0.f));
+        return DV_OK;
+      }
       // (rows of a padded row space - Builder::pitch - are skipped: B pieces of T frames, Tp frames apart)
       HIPCHK(hipMemcpy2D(host_out, (size_t)p.T * p.C * sizeof(float), p.p, (size_t)p.Tp * p.C * sizeof(float),
                          (size_t)p.T * p.C * sizeof(float), (size_t)u->B, hipMemcpyDeviceToHost));
@@ -2452,6 +2471,17 @@ extern "C" int dv_unet_probe(dv_unet* u, const char* name, float* host_out, int6
     }
   }
   return dv_fail(DV_ERR_INVALID, "no probe named %s (prepare with DVITS_KEEP_INTERMEDIATES=1)", name);
+}
+
+extern "C" int dv_unet_probe(dv_unet* u, const char* name, float* host_out, int64_t capacity, int64_t* dims) {
+  if (!u || !name) return dv_fail(DV_ERR_INVALID, "dv_unet_probe: null argument");
+  return probe_copy(u, name, host_out, capacity, dims);
+}
+
+extern "C" int dv_penc_probe(dv_penc* p, const char* name, float* host_out, int64_t capacity, int64_t* dims) {
+  if (!p || !name) return dv_fail(DV_ERR_INVALID, "dv_penc_probe: null argument");
+  if (!p->core.prepared) return dv_fail(DV_ERR_STATE, "dv_penc_probe before dv_penc_prepare");
+  return probe_copy(&p->core, name, host_out, capacity, dims);
 }
 
 // ----------------------------------------------------------------------------- single-operator entry points

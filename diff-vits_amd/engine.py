@@ -609,3 +609,12 @@ class PromptEncoderEngine:
         n, f = C.c_int64(), C.c_double()
         _lib.check(_lib.lib().dv_penc_stats(self._h, C.byref(n), C.byref(f)), "dv_penc_stats")
         return n.value, f.value
+
+    def probe(self, name):
+        """Named intermediate [B, L, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1 at prepare time)."""
+        dims = (C.c_int64 * 3)()
+        _lib.check(_lib.lib().dv_penc_probe(self._h, name.encode(), None, 0, dims), "dv_penc_probe")
+        out = torch.empty(tuple(dims), dtype=torch.float32)
+        _lib.check(_lib.lib().dv_penc_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims),
+                   "dv_penc_probe")
+        return out

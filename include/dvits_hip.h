@@ -269,6 +269,12 @@ int dv_penc_prepare(dv_penc* p, int32_t B, int32_t L, int32_t precision);
  * value transposed (model3.py:912 feeds prompt.transpose(1,2) to the UNet), padding frames zero. */
 int dv_penc_forward(dv_penc* p, const float* prompt, const float* keep, float* out, void* stream);
 int dv_penc_stats(dv_penc* p, int64_t* n_launch, double* flops);
+/* Debug/parity probe, the contract of dv_unet_probe: a named intermediate (channels-last [B, L, C]) of the last
+ * dv_penc_forward, copied to the host; only after a dv_penc_prepare with DVITS_KEEP_INTERMEDIATES=1.  Names: "pre",
+ * "layerN.attn" (after the attention out-projection + residual + mask), "layerN.ffn1" (the ReLU'd 4H-wide product,
+ * joined from its split planes and scaled by ffn_kernel^-1/2 as the reference has it; padding frames are NOT masked
+ * there, in the reference neither), "layerN" (the layer's output), "out_proj" (before the last LayerNorm). */
+int dv_penc_probe(dv_penc* p, const char* name, float* host_out, int64_t capacity, int64_t* dims);
 
 /* ---- single-operator entry points (parity tests of each kernel through the C ABI) ---- */
 
