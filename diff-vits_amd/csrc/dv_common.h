@@ -438,3 +438,8 @@ hipError_t launch_fill_f32(float* dst, float v, int64_t n, hipStream_t st);
 // sampler update: out = c[0]*x + c[1]*m0 + c[2]*m1 + c[3]*m2 + c[4]*m3 (coefficient row of 8 floats on device)
 hipError_t launch_lincomb(float* out, const float* x, const float* m0, const float* m1, const float* m2,
                           const float* m3, const float* coef, int64_t n, hipStream_t st);
+// dynamic thresholding of a data prediction, in place (kernels_thresh.hip): per row s = max(quantile(|x|, ratio), max_val),
+// x <- clamp(x, -s, s) / s over x [rows, n].  Five launches, no host synchronisation, no allocation: ws holds
+// dyn_thresh_ws_bytes(rows) bytes (any content); s_out [rows] receives s (null: not wanted).  rows <= 2048, n < 2^31.
+size_t dyn_thresh_ws_bytes(int rows);
+hipError_t launch_dyn_thresh(float* x, int rows, int64_t n, float ratio, float max_val, uint32_t* ws, float* s_out, hipStream_t st);

@@ -177,6 +177,10 @@ struct dv_plan {
   float* d_coefs = nullptr;
   float* d_tin = nullptr; int tin_B = 0;
   float* xp = nullptr; std::vector<float*> m; int64_t buf_numel = 0;
+  // dynamic thresholding of the data prediction of the evaluations in thr_mask (dv_plan_set_thresholding); thr_ratio < 0: off
+  double thr_ratio = -1.0, thr_max = 1.0;
+  std::vector<uint8_t> thr_mask;      // per EVAL
+  uint32_t* thr_ws = nullptr; int thr_rows = 0;
   // graph cache
   hipGraphExec_t exec = nullptr; hipStream_t cap_stream = nullptr;
   struct { dv_unet* u = nullptr; int64_t gen = -1; float* x = nullptr; const float* cond = nullptr; } key;
@@ -640,6 +644,7 @@ extern "C" void dv_plan_destroy(dv_plan* p) {
   if (p->d_tin) (void)hipFree(p->d_tin);
   if (p->xp) (void)hipFree(p->xp);
   for (float* b : p->m) (void)hipFree(b);
+  if (p->thr_ws) (void)hipFree(p->thr_ws);
   delete p;
 }
 
@@ -684,7 +689,34 @@ extern "C" int dv_plan_events(const dv_plan* p, int32_t* n_events, int32_t* ev9,
   return DV_OK;
 }
 
-static int plan_buffers(dv_plan* p, int64_t numel, int B) {
+extern "C" int dv_plan_set_thresholding(dv_plan* p, double ratio, double max_val, const uint8_t* eval_mask) {
+  if (!p) return dv_fail(DV_ERR_INVALID, "dv_plan_set_thresholding: null plan");
+  if (ratio < 0.0) {                     // off
+    if (p->thr_ratio >= 0.0) plan_drop_graph(p);
+    p->thr_ratio = -1.0; p->thr_mask.clear();
+    return DV_OK;
+  }
+  if (!(ratio <= 1.0)) return dv_fail(DV_ERR_INVALID, "dv_plan_set_thresholding: ratio %g is outside [0, 1]", ratio);
+  if (!(max_val > 0.0) || !std::isfinite(max_val))
+    return dv_fail(DV_ERR_INVALID, "dv_plan_set_thresholding: max_val %g must be positive and finite", max_val);
+  const size_t nfe = p->t_input.size();
+  std::vector<uint8_t> mask(nfe, 1);
+  if (eval_mask) for (size_t e = 0; e < nfe; ++e) mask[e] = eval_mask[e] ? 1 : 0;
+  if (!(p->thr_ratio == ratio && p->thr_max == max_val && p->thr_mask == mask)) plan_drop_graph(p);
+  p->thr_ratio = ratio; p->thr_max = max_val; p->thr_mask = mask;
+  return DV_OK;
+}
+
+// rows: utterances in x (the rows of the thresholding; 0 for a plan without it)
+static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows) {
+  if (p->thr_ratio >= 0.0 && p->thr_rows != rows) {
+    plan_drop_graph(p);
+    HIPCHK(hipDeviceSynchronize());     // (as for xp / the history slots below: an earlier run may still be using the old workspace)
+    if (p->thr_ws) (void)hipFree(p->thr_ws);
+    p->thr_ws = nullptr; p->thr_rows = 0;
+    HIPCHK(hipMalloc((void**)&p->thr_ws, dyn_thresh_ws_bytes(rows)));
+    p->thr_rows = rows;
+  }
   if (!p->d_coefs) {
     HIPCHK(hipMalloc((void**)&p->d_coefs, p->coefs.size() * 8 * sizeof(float)));
     HIPCHK(hipMemcpy(p->d_coefs, p->coefs.data(), p->coefs.size() * 8 * sizeof(float), hipMemcpyHostToDevice));
@@ -719,11 +751,18 @@ static int plan_buffers(dv_plan* p, int64_t numel, int B) {
 }
 
 template <typename EvalFn>
-static int run_events(dv_plan* p, float* x, int64_t numel, EvalFn eval, hipStream_t st) {
+static int run_events(dv_plan* p, float* x, int64_t numel, int rows, EvalFn eval, hipStream_t st) {
+  const bool thr = p->thr_ratio >= 0.0;
   for (const Event& e : p->ev) {
     if (e.type == 0) {
       int rc = eval(e.src == 0 ? x : p->xp, e.eval_idx, p->m[e.dst]);
       if (rc != DV_OK) return rc;
+      // correcting_x0_fn = dynamic thresholding (dpm_solver.py:443-444, uni_pc.py:292-293): on the data prediction, before
+      // anything reads it - in the noise forms the in-place x0 -> noise COMB of this slot follows (Plan.run_python: x0_hook)
+      if (thr && p->thr_mask[e.eval_idx]) {
+        hipError_t he = launch_dyn_thresh(p->m[e.dst], rows, numel / rows, (float)p->thr_ratio, (float)p->thr_max, p->thr_ws, nullptr, st);
+        if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "dynamic thresholding launch failed: %s", hipGetErrorString(he));
+      }
     } else {
       const float* ms[4];
       for (int k = 0; k < 4; ++k) ms[k] = e.slots[k] >= 0 ? p->m[e.slots[k]] : nullptr;
@@ -745,7 +784,7 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
   if (cin > cout && !cond) return dv_fail(DV_ERR_INVALID, "dv_sampler_run: cond is required (in_channels > out_channels)");
   if (int hrc = dv_unet_health(u)) return hrc;
   const int64_t numel = (int64_t)B * cout * T;
-  int rc = plan_buffers(p, numel, B);
+  int rc = plan_buffers(p, numel, B, B);
   if (rc != DV_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the time-embedding chain of every evaluation runs once, at the head of the loop (the timesteps of the plan are known)
@@ -759,7 +798,7 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
   if (ng && ng[0] == '1') {
     const int tb = dv_unet_temb_all(u, p->d_tin, nfe, st);
     if (tb < 0) return tb;
-    return run_events(p, x_inout, numel, eval(st, tb == 0), st);
+    return run_events(p, x_inout, numel, B, eval(st, tb == 0), st);
   }
 
   if (!(p->exec && p->key.u == u && p->key.gen == gen && p->key.x == x_inout && p->key.cond == cond)) {
@@ -773,7 +812,7 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
     }
     HIPCHK(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
     const int tb = dv_unet_temb_all(u, p->d_tin, nfe, p->cap_stream);
-    rc = tb < 0 ? tb : run_events(p, x_inout, numel, eval(p->cap_stream, tb == 0), p->cap_stream);
+    rc = tb < 0 ? tb : run_events(p, x_inout, numel, B, eval(p->cap_stream, tb == 0), p->cap_stream);
     hipError_t ce = hipStreamEndCapture(p->cap_stream, &graph);
     if (rc != DV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     if (ce != hipSuccess) return dv_fail(DV_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
@@ -786,16 +825,47 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
   return DV_OK;
 }
 
-extern "C" int dv_sampler_run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int64_t numel, void* stream) {
-  if (!p || !fn || !x_inout || numel <= 0) return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: bad argument");
+static int run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int rows, int64_t numel, void* stream, const char* who) {
   if ((uintptr_t)x_inout % 16 != 0)   // k_lincomb reads and writes x as float4
-    return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: x_inout (%p) must be 16-byte aligned", (void*)x_inout);
-  int rc = plan_buffers(p, numel, 0);
+    return dv_fail(DV_ERR_INVALID, "%s: x_inout (%p) must be 16-byte aligned", who, (void*)x_inout);
+  int rc = plan_buffers(p, numel, 0, rows);
   if (rc != DV_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   auto eval = [&](const float* src, int idx, float* dst) {
     int r = fn(user, src, p->t_input[idx], dst, (void*)st);
     return r == 0 ? DV_OK : dv_fail(DV_ERR_INVALID, "model callback failed with %d", r);
   };
-  return run_events(p, x_inout, numel, eval, st);
+  return run_events(p, x_inout, numel, rows, eval, st);
+}
+
+extern "C" int dv_sampler_run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int64_t numel, void* stream) {
+  if (!p || !fn || !x_inout || numel <= 0) return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: bad argument");
+  if (p->thr_ratio >= 0.0)
+    return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: the plan thresholds per row and this form has no row count - use "
+                                   "dv_sampler_run_custom_rows");
+  return run_custom(p, fn, user, x_inout, 0, numel, stream, "dv_sampler_run_custom");
+}
+
+extern "C" int dv_sampler_run_custom_rows(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int32_t rows, int64_t numel,
+                                          void* stream) {
+  if (!p || !fn || !x_inout || numel <= 0 || rows <= 0 || rows > 2048 || numel % rows != 0)
+    return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom_rows: bad argument (rows in 1..2048 must divide numel)");
+  return run_custom(p, fn, user, x_inout, rows, numel, stream, "dv_sampler_run_custom_rows");
+}
+
+extern "C" int dv_op_dynamic_threshold(float* x0_inout, int32_t rows, int64_t row_numel, double ratio, double max_val, float* s_out,
+                                       void* stream) {
+  if (!x0_inout || rows < 1 || rows > 2048 || row_numel < 1 || row_numel > (int64_t)INT32_MAX || (uintptr_t)x0_inout % 4 != 0)
+    return dv_fail(DV_ERR_INVALID, "dv_op_dynamic_threshold: bad argument (rows in 1..2048, 1 <= row_numel < 2^31)");
+  if (!(ratio >= 0.0 && ratio <= 1.0)) return dv_fail(DV_ERR_INVALID, "dv_op_dynamic_threshold: ratio %g is outside [0, 1]", ratio);
+  if (!(max_val > 0.0) || !std::isfinite(max_val))
+    return dv_fail(DV_ERR_INVALID, "dv_op_dynamic_threshold: max_val %g must be positive and finite", max_val);
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* ws = nullptr;
+  HIPCHK(hipMalloc((void**)&ws, dyn_thresh_ws_bytes(rows)));
+  hipError_t he = launch_dyn_thresh(x0_inout, rows, row_numel, (float)ratio, (float)max_val, ws, s_out, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  (void)hipFree(ws);
+  if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_dynamic_threshold failed: %s", hipGetErrorString(he));
+  return DV_OK;
 }

@@ -6,6 +6,7 @@ UNet schedule + fused update kernels) when the model is this package's UNet.
 import ctypes as C
 import os
 import importlib
+import sys
 
 import numpy as np
 import torch
@@ -174,10 +175,13 @@ def wrap_model(model, noise_schedule, model_type="noise", model_kwargs={}, guida
 
 
 class Plan:
-    """Compiled multistep loop: events + fp64-derived coefficient rows."""
+    """Compiled multistep loop: events + fp64-derived coefficient rows.
+    `thresholding=(ratio, max_val, mask)`: dynamic thresholding of the data prediction as part of the native loop
+    (dv_plan_set_thresholding) - `mask` a tuple of nfe truth values, the evaluations it applies to (None: all).  It does not
+    change the tables: `run_python` takes it, like every correction, as its `x0_hook`."""
 
     def __init__(self, solver, betas, steps, order, skip_type, lower_order_final, t_start=None, t_end=None,
-                 denoise_to_zero=False, schedule=("discrete", 0.0, 0.0), method="multistep"):
+                 denoise_to_zero=False, schedule=("discrete", 0.0, 0.0), method="multistep", thresholding=None):
         L = _lib()
         self.method = method
         for name, v in (("t_start", t_start), ("t_end", t_end)):
@@ -188,7 +192,8 @@ class Plan:
             raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'"
                              .format(skip_type))
         betas = np.ascontiguousarray(betas, dtype=np.float32)
-        self._args = (solver, betas, steps, order, skip_type, lower_order_final, t_start, t_end, denoise_to_zero, schedule, method)
+        self._args = (solver, betas, steps, order, skip_type, lower_order_final, t_start, t_end, denoise_to_zero, schedule, method,
+                      thresholding)
         self._per_shape = {}          # captured graphs live in the native plan, one per plan: a copy per input shape
         self._h = C.c_void_p()
         L.check(L.lib().dv_sampler_plan_method(solver, L.SCHEDULE[schedule[0]], betas.ctypes.data_as(C.c_void_p), len(betas),
@@ -217,6 +222,27 @@ class Plan:
         self.events = np.zeros((ne.value, 9), dtype=np.int32)
         self.n_slots = ns.value
         L.check(L.lib().dv_plan_events(self._h, None, self.events.ctypes.data_as(C.c_void_p), None), "dv_plan_events")
+        self.thresholding = None
+        if thresholding is not None:
+            self.set_thresholding(thresholding)
+
+    def set_thresholding(self, thresholding):
+        """(ratio, max_val, mask | None) switches the native loop's dynamic thresholding on, None off; either way the plan's
+        captured graph is dropped.  Copies made by for_shape before the call keep what they were made with."""
+        L = _lib()
+        if thresholding is None:
+            L.check(L.lib().dv_plan_set_thresholding(self._h, -1.0, 1.0, None), "dv_plan_set_thresholding")
+        else:
+            ratio, max_val, mask = thresholding
+            buf = None
+            if mask is not None:
+                if len(mask) != self.nfe:
+                    raise ValueError("thresholding mask has %d entries, the plan %d evaluations" % (len(mask), self.nfe))
+                buf = (C.c_uint8 * self.nfe)(*[1 if v else 0 for v in mask])
+                thresholding = (ratio, max_val, tuple(bool(v) for v in mask))
+            L.check(L.lib().dv_plan_set_thresholding(self._h, float(ratio), float(max_val), buf), "dv_plan_set_thresholding")
+        self.thresholding = thresholding
+        self._args = self._args[:11] + (thresholding,)
 
     def for_shape(self, shape):
         """The plan whose captured hipGraph belongs to inputs of this shape (this one for the first shape seen, a copy
@@ -233,7 +259,9 @@ class Plan:
     def __del__(self):
         try:
             if getattr(self, "_h", None) and self._h.value:
-                _lib().lib().dv_plan_destroy(self._h)
+                # (no import from a finaliser: a collection can run it inside an import of the same thread.  A plan that
+                # exists was made through the loaded module, so it is in sys.modules until the interpreter shuts down)
+                sys.modules["diff_vits_amd._lib"].lib().dv_plan_destroy(self._h)
                 self._h = C.c_void_p()
         except Exception:
             pass
@@ -370,6 +398,18 @@ def dynamic_thresholding(x0, ratio, max_val):
     return torch.clamp(x0, -s, s) / s
 
 
+def native_graph_model(model_fn, x):
+    """The NativeUNetModel behind `model_fn` if a run on `x` can be replayed as one graph (this package's UNet on the HIP
+    engine, a CUDA tensor, no model kwargs), else None.  Corrections and intermediates are the caller's to rule out."""
+    info = getattr(model_fn, "_dv", None)
+    if info is None or info["model_type"] != "x_start":
+        return None
+    raw = info["model"]
+    if isinstance(raw, NativeUNetModel) and x.is_cuda and raw.unet.backend == "hip" and not info["model_kwargs"]:
+        return raw
+    return None
+
+
 def sample_with_plan(plan, model_fn, noise_schedule, x, intermediates=None, x0_hook=None, xt_hook=None):
     """Run a compiled loop for a solver-level `model_fn` (noise prediction, as returned by
     model_wrapper or supplied by the user).  With `intermediates` (a list to fill) or a correction hook the loop runs step
@@ -380,9 +420,10 @@ def sample_with_plan(plan, model_fn, noise_schedule, x, intermediates=None, x0_h
     with torch.no_grad():
         if info is not None and info["model_type"] == "x_start":
             raw = info["model"]
-            if (isinstance(raw, NativeUNetModel) and x.is_cuda and raw.unet.backend == "hip" and not info["model_kwargs"]
-                    and intermediates is None and x0_hook is None and xt_hook is None):
+            if native_graph_model(model_fn, x) is not None and intermediates is None and x0_hook is None and xt_hook is None:
                 return raw.run_plan(plan, x)
+            # (a plan with thresholding compiled in runs natively only: stepped, the correction is the x0_hook)
+            assert plan.thresholding is None or x0_hook is not None, "a thresholded plan stepped without its x0_hook"
             kwargs = info["model_kwargs"]
 
             def data_model(xx, eidx):

@@ -7,7 +7,7 @@ coefficients and replayed natively or around a Python callable.  Unlike the refe
 'x_start' wrapper (uni_pc.py:189-191, which only broadcasts correctly at B == 1) the batch
 broadcast here is the intended per-sample one; at B == 1 both coincide.
 """
-from ._plan import NativeUNetModel, NoiseScheduleBase, Plan, dynamic_thresholding, sample_with_plan, wrap_model
+from ._plan import NativeUNetModel, NoiseScheduleBase, Plan, dynamic_thresholding, native_graph_model, sample_with_plan, wrap_model
 
 __all__ = ["NoiseScheduleVP", "model_wrapper", "UniPC", "NativeUNetModel"]
 
@@ -29,8 +29,11 @@ class UniPC:
                  correcting_xt_fn=None, thresholding_max_val=1.0, dynamic_thresholding_ratio=0.995, variant="bh1"):
         assert algorithm_type in ["data_prediction", "noise_prediction"]
         # correcting_x0_fn ("dynamic_thresholding" or fn(x0)) / correcting_xt_fn (fn(x, t, step)): reference :256-261, 292-293.
-        # With either the loop is stepped from Python, never replayed as one graph.
+        # With a callable the loop is stepped from Python, never replayed as one graph; dynamic thresholding is compiled into
+        # the native plan whenever the run would otherwise be a graph replay (sample(); see dpm_solver.py).
+        self._thresholding = None
         if correcting_x0_fn == "dynamic_thresholding":
+            self._thresholding = (float(dynamic_thresholding_ratio), float(thresholding_max_val))
             correcting_x0_fn = lambda x0: dynamic_thresholding(x0, dynamic_thresholding_ratio, thresholding_max_val)
         self.correcting_x0_fn, self.correcting_xt_fn = correcting_x0_fn, correcting_xt_fn
         if variant not in _SOLVERS:
@@ -41,12 +44,14 @@ class UniPC:
         self.predict_x0 = algorithm_type == "data_prediction"    # (False: the same updates on the noise prediction, uni_pc.py:266)
         self._plans = {}
 
-    def _plan(self, steps, order, skip_type, lower_order_final, t_start=None, t_end=None, denoise_to_zero=False):
+    def _plan(self, steps, order, skip_type, lower_order_final, t_start=None, t_end=None, denoise_to_zero=False, thresholding=None):
         key = (steps, order, skip_type, bool(lower_order_final), t_start, t_end, bool(denoise_to_zero))
+        if thresholding is not None:       # (a thresholded graph and a plain one never share a handle)
+            key += (thresholding,)
         if key not in self._plans:
             self._plans[key] = Plan(_SOLVERS[self.variant] + (0 if self.predict_x0 else 6), self.noise_schedule._betas, steps, order, skip_type,
                                     lower_order_final, t_start, t_end, denoise_to_zero,
-                                    schedule=self.noise_schedule._plan_schedule())
+                                    schedule=self.noise_schedule._plan_schedule(), thresholding=thresholding)
         return self._plans[key]
 
     def sample(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep",
@@ -64,6 +69,13 @@ class UniPC:
         # 'noise_prediction' only the final denoise_to_zero evaluation goes through it, :279-281)
         last = plan.nfe - 1
         keep = (lambda eidx: True) if self.predict_x0 else (lambda eidx: denoise_to_zero and eidx == last)
+        if (self._thresholding is not None and self.correcting_xt_fn is None and not return_intermediate
+                and native_graph_model(self.model_fn, x) is not None):
+            mask = tuple(bool(keep(e)) for e in range(plan.nfe))       # dynamic thresholding inside the graph
+            if any(mask):
+                plan = self._plan(steps, order, skip_type, lower_order_final, t_start, t_end, denoise_to_zero,
+                                  thresholding=self._thresholding + (mask,))
+            return sample_with_plan(plan, self.model_fn, self.noise_schedule, x)
         hooks = dict(x0_hook=None if fn0 is None else (lambda x0, eidx: fn0(x0) if keep(eidx) else x0), xt_hook=self.correcting_xt_fn)
         if not return_intermediate:
             return sample_with_plan(plan, self.model_fn, self.noise_schedule, x, **hooks)

@@ -252,6 +252,19 @@ int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const float* cond, vo
 typedef int (*dv_model_fn)(void* user, const float* x, double t_input, float* out, void* stream);
 int dv_sampler_run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int64_t numel, void* stream);
 
+/* correcting_x0_fn='dynamic_thresholding' of DPM_Solver / UniPC (dpm_solver.py:409-425, 433-445; uni_pc.py:256-277, 292-293) as
+ * part of the compiled loop: after every evaluation e with eval_mask[e] != 0 (HOST uint8[nfe]; NULL: all of them) the data
+ * prediction is replaced, per utterance, by clamp(x0, -s, s) / s with s = max(quantile(|x0|, ratio), max_val) - before
+ * anything reads it (in the noise forms the x0 -> noise conversion sees the thresholded x0).  Which evaluations the
+ * reference thresholds is the caller's rule (all of them for 'dpmsolver++' / 'data_prediction'; only the final
+ * denoise_to_zero evaluation otherwise).  ratio < 0 switches it off again; ratio > 1, or max_val <= 0 or not finite:
+ * DV_ERR_INVALID.  Any change drops the captured graph.  dv_sampler_run thresholds per row of its batch; a plan with
+ * thresholding is refused by dv_sampler_run_custom (DV_ERR_INVALID), which does not know the rows: */
+int dv_plan_set_thresholding(dv_plan* p, double ratio, double max_val, const uint8_t* eval_mask);
+/* dv_sampler_run_custom with x_inout as [rows, numel / rows] (rows in 1..2048, numel % rows == 0), for plans with and
+ * without thresholding. */
+int dv_sampler_run_custom_rows(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int32_t rows, int64_t numel, void* stream);
+
 /* ---- prompt encoder: PromptEncoder.forward, reference model3.py:408-433 ------------------
  * The reference recomputes it inside every denoiser call (Diffusion_Encoder.forward, model3.py:902-906) although it
  * does not depend on the step; the host mirror calls this once per sampler run and feeds the result to
@@ -317,6 +330,13 @@ int dv_op_attention_frag(const float* q, const float* k, const float* v, const f
  * kernel is an error (-1), never a silent fall-back. */
 int dv_op_conv3(const float* x, const float* w, const float* bias, const float* x_sc, const float* w_sc, float* y, int32_t B,
                 int32_t Cin, int32_t T, int32_t Tp, int32_t Cout, int32_t Csc, int32_t up2, void* stream);
+/* Dynamic thresholding on the kernels the sampler loop runs (k_thr_*): in place on x0_inout [rows, row_numel] (rows in 1..2048,
+ * row_numel < 2^31, any 4-byte aligned address), per row s = max(quantile(|x0|, ratio), max_val) - torch.quantile's linear
+ * interpolation on float32, the two order statistics found exactly by radix select - and x0 <- clamp(x0, -s, s) / s.  A row
+ * with a NaN becomes NaN.  s_out [rows] (device, or NULL) receives s.  ratio outside [0, 1], max_val <= 0 or not finite:
+ * DV_ERR_INVALID before anything is launched. */
+int dv_op_dynamic_threshold(float* x0_inout, int32_t rows, int64_t row_numel, double ratio, double max_val, float* s_out,
+                            void* stream);
 
 #ifdef __cplusplus
 }
