@@ -81,6 +81,10 @@ SIGNATURES = {
     "dv_plan_set_thresholding": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "dv_sampler_run_custom_rows": (C.c_int, [C.c_void_p, MODEL_FN, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "dv_op_dynamic_threshold": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "dv_plan_set_guidance": (C.c_int, [C.c_void_p, C.c_double, C.c_int32]),
+    "dv_op_cfg_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p]),
+    "dv_op_cfg_pair_in": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "dv_plan_graph_nodes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dv_op_conv1d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p]),
     "dv_op_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
     "dv_op_linear_planes": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 6 + [C.c_void_p]),

@@ -443,3 +443,7 @@ hipError_t launch_lincomb(float* out, const float* x, const float* m0, const flo
 // dyn_thresh_ws_bytes(rows) bytes (any content); s_out [rows] receives s (null: not wanted).  rows <= 2048, n < 2^31.
 size_t dyn_thresh_ws_bytes(int rows);
 hipError_t launch_dyn_thresh(float* x, int rows, int64_t n, float ratio, float max_val, uint32_t* ws, float* s_out, hipStream_t st);
+// classifier-free guidance around one evaluation of the sampler loop (kernels_guide.hip), flat over n floats (any n >= 1, any
+// 4-byte aligned addresses): out[0 .. n) = out[n .. 2 n) = in;  out[i] = fmaf(g, pair[n + i] - pair[i], pair[i]).  One launch each.
+hipError_t launch_cfg_pair_in(const float* in, float* out, int64_t n, hipStream_t st);
+hipError_t launch_cfg_combine(const float* pair, float* out, int64_t n, float g, hipStream_t st);

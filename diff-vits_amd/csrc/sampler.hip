@@ -13,6 +13,8 @@
 // Deviation from the reference, documented in DESIGN.md section 5: the x0 -> noise -> x0 round trip of
 // model_wrapper/data_prediction_fn (dpm_solver.py:290-292, 433-442) is algebraically the
 // identity and is not replayed.
+// Classifier-free guidance (dv_plan_set_guidance) wraps every EVAL: [x | x] -> the network at 2B rows -> x0_u + g (x0_c - x0_u)
+// into the history slot (kernels_guide.hip) - the reference's guided noise is linear in the two data predictions.
 #include "../../include/dvits_hip.h"
 #include "dv_common.h"
 
@@ -181,8 +183,15 @@ struct dv_plan {
   double thr_ratio = -1.0, thr_max = 1.0;
   std::vector<uint8_t> thr_mask;      // per EVAL
   uint32_t* thr_ws = nullptr; int thr_rows = 0;
+  // classifier-free guidance (dv_plan_set_guidance): every evaluation runs the network on [x | x] with the conditioning
+  // [uncond | cond] and reduces the pair of data predictions to x0_u + g (x0_c - x0_u) (kernels_guide.hip).  The 2B-row
+  // staging buffers are the plan's: network input, network output, channel-concat condition (duplicated once per run)
+  bool cfg_on = false; double cfg_scale = 1.0;
+  float* cfg_in = nullptr; float* cfg_out = nullptr; int64_t cfg_numel = 0;      // 2 * numel floats each
+  float* cfg_cond = nullptr; int64_t cfg_cond_numel = 0;                        // 2 * the condition's floats
   // graph cache
   hipGraphExec_t exec = nullptr; hipStream_t cap_stream = nullptr;
+  int64_t graph_nodes = 0;            // nodes of the captured graph (dv_plan_graph_nodes); 0 while there is none
   struct { dv_unet* u = nullptr; int64_t gen = -1; float* x = nullptr; const float* cond = nullptr; } key;
 };
 
@@ -632,6 +641,7 @@ extern "C" int dv_sampler_plan_method(int32_t solver, int32_t schedule, const fl
 
 static void plan_drop_graph(dv_plan* p) {
   if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
+  p->graph_nodes = 0;
   p->key.u = nullptr; p->key.gen = -1; p->key.x = nullptr; p->key.cond = nullptr;
 }
 
@@ -645,6 +655,7 @@ extern "C" void dv_plan_destroy(dv_plan* p) {
   if (p->xp) (void)hipFree(p->xp);
   for (float* b : p->m) (void)hipFree(b);
   if (p->thr_ws) (void)hipFree(p->thr_ws);
+  for (float* b : {p->cfg_in, p->cfg_out, p->cfg_cond}) if (b) (void)hipFree(b);
   delete p;
 }
 
@@ -707,8 +718,39 @@ extern "C" int dv_plan_set_thresholding(dv_plan* p, double ratio, double max_val
   return DV_OK;
 }
 
-// rows: utterances in x (the rows of the thresholding; 0 for a plan without it)
-static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows) {
+// nodes of the captured graph of the last dv_sampler_run (0: none - never run, dropped, or DVITS_NO_GRAPH)
+extern "C" int dv_plan_graph_nodes(const dv_plan* p, int64_t* n_nodes) {
+  if (!p || !n_nodes) return dv_fail(DV_ERR_INVALID, "dv_plan_graph_nodes: null argument");
+  *n_nodes = p->graph_nodes;
+  return DV_OK;
+}
+
+extern "C" int dv_plan_set_guidance(dv_plan* p, double scale, int32_t on) {
+  if (!p) return dv_fail(DV_ERR_INVALID, "dv_plan_set_guidance: null plan");
+  if (!on) {
+    if (p->cfg_on) plan_drop_graph(p);
+    p->cfg_on = false; p->cfg_scale = 1.0;
+    return DV_OK;
+  }
+  if (!std::isfinite(scale)) return dv_fail(DV_ERR_INVALID, "dv_plan_set_guidance: scale %g must be finite", scale);
+  if (!(p->cfg_on && p->cfg_scale == scale)) plan_drop_graph(p);
+  p->cfg_on = true; p->cfg_scale = scale;
+  return DV_OK;
+}
+
+// rows: utterances in x (the rows of the thresholding; 0 for a plan without it); B: rows of the network's batch (2 x rows of x
+// under guidance); cond_numel: floats of the channel-concat condition that goes with x (guidance stages it twice)
+static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows, int64_t cond_numel = 0) {
+  if (p->cfg_on && (p->cfg_numel != numel || p->cfg_cond_numel != cond_numel)) {
+    plan_drop_graph(p);
+    HIPCHK(hipDeviceSynchronize());     // (an earlier run may still be using the old buffers)
+    for (float** b : {&p->cfg_in, &p->cfg_out, &p->cfg_cond}) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    p->cfg_numel = 0; p->cfg_cond_numel = 0;
+    HIPCHK(hipMalloc((void**)&p->cfg_in, 2 * numel * sizeof(float)));
+    HIPCHK(hipMalloc((void**)&p->cfg_out, 2 * numel * sizeof(float)));
+    if (cond_numel > 0) HIPCHK(hipMalloc((void**)&p->cfg_cond, 2 * cond_numel * sizeof(float)));
+    p->cfg_numel = numel; p->cfg_cond_numel = cond_numel;
+  }
   if (p->thr_ratio >= 0.0 && p->thr_rows != rows) {
     plan_drop_graph(p);
     HIPCHK(hipDeviceSynchronize());     // (as for xp / the history slots below: an earlier run may still be using the old workspace)
@@ -782,22 +824,46 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
   int B, T, cin, cout; int64_t gen;
   if (!dv_unet_dims(u, &B, &T, &cin, &cout, &gen)) return dv_fail(DV_ERR_STATE, "dv_sampler_run: unet not prepared / cond not set");
   if (cin > cout && !cond) return dv_fail(DV_ERR_INVALID, "dv_sampler_run: cond is required (in_channels > out_channels)");
+  // guidance: the network runs at 2B rows (dv_unet_prepare), x_inout and cond hold B
+  const bool cfg = p->cfg_on;
+  if (cfg && B % 2 != 0)
+    return dv_fail(DV_ERR_INVALID, "dv_sampler_run: a guided plan needs the unet prepared at an even batch 2B (x_inout holds B rows), got %d", B);
   if (int hrc = dv_unet_health(u)) return hrc;
-  const int64_t numel = (int64_t)B * cout * T;
-  int rc = plan_buffers(p, numel, B, B);
+  const int Bn = B;                   // rows of the network's batch
+  if (cfg) B /= 2;                    // rows of x
+  if (cin <= cout) cond = nullptr;    // (no channel-concat condition: the pointer is ignored, as dv_unet_enqueue ignores it)
+  const int64_t numel = (int64_t)B * cout * T, cond_numel = cond ? (int64_t)B * (cin - cout) * T : 0;
+  int rc = plan_buffers(p, numel, Bn, B, cond_numel);
   if (rc != DV_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the time-embedding chain of every evaluation runs once, at the head of the loop (the timesteps of the plan are known)
   const int nfe = (int)p->t_input.size();
+  const float g = (float)p->cfg_scale;
+  const float* const net_cond = cfg && cond ? p->cfg_cond : cond;
   auto eval = [&](hipStream_t s, bool batched) {
     return [=](const float* src, int idx, float* dst) {
-      return dv_unet_enqueue(u, src, cout, cond, p->d_tin + (size_t)idx * B, dst, s, batched ? idx : -1);
+      if (!cfg) return dv_unet_enqueue(u, src, cout, cond, p->d_tin + (size_t)idx * Bn, dst, s, batched ? idx : -1);
+      // [x | x] -> the network at 2B rows (conditioning [uncond | cond]: dv_unet_set_cond) -> x0_u + g (x0_c - x0_u)
+      hipError_t he = launch_cfg_pair_in(src, p->cfg_in, numel, s);
+      if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "guidance input launch failed: %s", hipGetErrorString(he));
+      int r = dv_unet_enqueue(u, p->cfg_in, cout, net_cond, p->d_tin + (size_t)idx * Bn, p->cfg_out, s, batched ? idx : -1);
+      if (r != DV_OK) return r;
+      he = launch_cfg_combine(p->cfg_out, dst, numel, g, s);
+      if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "guidance combine launch failed: %s", hipGetErrorString(he));
+      return (int)DV_OK;
     };
+  };
+  // head of the loop under guidance: the channel-concat condition once for both halves
+  auto stage_cond = [&](hipStream_t s) -> int {
+    if (!(cfg && cond)) return DV_OK;
+    hipError_t he = launch_cfg_pair_in(cond, p->cfg_cond, cond_numel, s);
+    return he == hipSuccess ? (int)DV_OK : dv_fail(DV_ERR_HIP, "guidance condition launch failed: %s", hipGetErrorString(he));
   };
   const char* ng = getenv("DVITS_NO_GRAPH");
   if (ng && ng[0] == '1') {
     const int tb = dv_unet_temb_all(u, p->d_tin, nfe, st);
     if (tb < 0) return tb;
+    if ((rc = stage_cond(st)) != DV_OK) return rc;
     return run_events(p, x_inout, numel, B, eval(st, tb == 0), st);
   }
 
@@ -812,14 +878,18 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
     }
     HIPCHK(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
     const int tb = dv_unet_temb_all(u, p->d_tin, nfe, p->cap_stream);
-    rc = tb < 0 ? tb : run_events(p, x_inout, numel, B, eval(p->cap_stream, tb == 0), p->cap_stream);
+    rc = tb < 0 ? tb : stage_cond(p->cap_stream);
+    if (rc == DV_OK) rc = run_events(p, x_inout, numel, B, eval(p->cap_stream, tb == 0), p->cap_stream);
     hipError_t ce = hipStreamEndCapture(p->cap_stream, &graph);
     if (rc != DV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     if (ce != hipSuccess) return dv_fail(DV_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+    size_t n_nodes = 0;
+    if (hipGraphGetNodes(graph, nullptr, &n_nodes) != hipSuccess) n_nodes = 0;
     hipError_t ie = hipGraphInstantiate(&p->exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ie != hipSuccess) { p->exec = nullptr; return dv_fail(DV_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie)); }
     p->key.u = u; p->key.gen = gen; p->key.x = x_inout; p->key.cond = cond;
+    p->graph_nodes = (int64_t)n_nodes;
   }
   HIPCHK(hipGraphLaunch(p->exec, st));
   return DV_OK;
@@ -828,6 +898,9 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
 static int run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int rows, int64_t numel, void* stream, const char* who) {
   if ((uintptr_t)x_inout % 16 != 0)   // k_lincomb reads and writes x as float4
     return dv_fail(DV_ERR_INVALID, "%s: x_inout (%p) must be 16-byte aligned", who, (void*)x_inout);
+  if (p->cfg_on)                      // (the callback evaluates one batch: it has no unconditional / conditional pair)
+    return dv_fail(DV_ERR_INVALID, "%s: the plan has classifier-free guidance, which runs in dv_sampler_run only (the model callback "
+                                   "has no pair of conditions) - switch it off with dv_plan_set_guidance(p, 1.0, 0)", who);
   int rc = plan_buffers(p, numel, 0, rows);
   if (rc != DV_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -867,5 +940,27 @@ extern "C" int dv_op_dynamic_threshold(float* x0_inout, int32_t rows, int64_t ro
   if (he == hipSuccess) he = hipStreamSynchronize(st);
   (void)hipFree(ws);
   if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_dynamic_threshold failed: %s", hipGetErrorString(he));
+  return DV_OK;
+}
+
+extern "C" int dv_op_cfg_combine(const float* x0_pair, float* out, int32_t rows, int64_t row_numel, double scale, void* stream) {
+  if (!x0_pair || !out || rows < 1 || rows > 2048 || row_numel < 1 || row_numel > (int64_t)INT32_MAX ||
+      (((uintptr_t)x0_pair | (uintptr_t)out) & 3u))
+    return dv_fail(DV_ERR_INVALID, "dv_op_cfg_combine: bad argument (rows in 1..2048, 1 <= row_numel < 2^31, 4-byte aligned pointers)");
+  if (!std::isfinite(scale)) return dv_fail(DV_ERR_INVALID, "dv_op_cfg_combine: scale %g must be finite", scale);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t he = launch_cfg_combine(x0_pair, out, (int64_t)rows * row_numel, (float)scale, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_cfg_combine failed: %s", hipGetErrorString(he));
+  return DV_OK;
+}
+
+extern "C" int dv_op_cfg_pair_in(const float* in, float* out, int64_t numel, void* stream) {
+  if (!in || !out || numel < 1 || numel > ((int64_t)1 << 40) || (((uintptr_t)in | (uintptr_t)out) & 3u))
+    return dv_fail(DV_ERR_INVALID, "dv_op_cfg_pair_in: bad argument (1 <= numel <= 2^40, 4-byte aligned pointers)");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t he = launch_cfg_pair_in(in, out, numel, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_cfg_pair_in failed: %s", hipGetErrorString(he));
   return DV_OK;
 }

@@ -316,10 +316,33 @@ class NaturalSpeech2(nn.Module):
         return self.diff_model(x, data, t)
 
     @torch.no_grad()
-    def sample_from_prior(self, content, refer, text_lengths, spec_lengths, vocos=None, sample_method="unipc", noise=None):
-        """(content, refer) -> (audio | None, mel): reference model3.py:1162-1203 after the `vits.infer` call."""
+    def _guidance_conditions(self, refer, spec_lengths, negative_refer, negative_lengths):
+        """(condition, mask, unconditional_condition, uncond_mask) of a classifier-free guided run: the prompt's encoder
+        states, and those of the negative prompt - the same prompt encoder, padded to the conditional length L - or, without
+        one, all-zero states under the conditional mask."""
+        enc, mask = self.diff_model._conditioning(refer, spec_lengths, torch.float32)
+        if negative_refer is None:
+            return enc, mask, torch.zeros_like(enc), mask
+        if negative_lengths is None:
+            negative_lengths = torch.full((negative_refer.shape[0],), negative_refer.shape[2], dtype=torch.long, device=negative_refer.device)
+        B, L, Ln = enc.shape[0], enc.shape[1], negative_refer.shape[2]
+        if negative_refer.shape[0] != B or Ln > L:
+            raise ValueError("negative_refer must be [B=%d, 100, L' <= %d], got %s" % (B, L, tuple(negative_refer.shape)))
+        nmask = sequence_mask(negative_lengths, Ln)
+        nenc = self.diff_model.prompt_encoder.encode_channels_last(negative_refer, negative_lengths) * nmask.unsqueeze(-1).to(enc.dtype)
+        return enc, mask, F.pad(nenc.to(enc), (0, 0, 0, L - Ln)), F.pad(nmask.to(torch.bool), (0, L - Ln))
+
+    @torch.no_grad()
+    def sample_from_prior(self, content, refer, text_lengths, spec_lengths, vocos=None, sample_method="unipc", noise=None,
+                          guidance_scale=1.0, negative_refer=None, negative_lengths=None):
+        """(content, refer) -> (audio | None, mel): reference model3.py:1162-1203 after the `vits.infer` call.
+        guidance_scale != 1: classifier-free guidance (model_wrapper(guidance_type='classifier-free'), dpm_solver.py:322-330)
+        between the speaker prompt and `negative_refer` [B, 100, L'] with `negative_lengths` (None: all-zero encoder states
+        under the prompt's mask) - on the HIP backend inside the one hipGraph, on the torch backend through the mirror's
+        generic path.  With the defaults nothing changes."""
         if sample_method not in ("unipc", "dpmsolver"):
             raise ValueError("sample_method %r is not supported (this build: 'unipc', 'dpmsolver')" % (sample_method,))
+        guided = float(guidance_scale) != 1.0
         shape = (content.shape[0], self.dim, content.shape[2])
         audio = torch.randn(shape, device=refer.device) if noise is None else noise.to(refer.device)
         if tuple(audio.shape) != shape:
@@ -330,7 +353,26 @@ class NaturalSpeech2(nn.Module):
             from .sampler.uni_pc import NoiseScheduleVP, UniPC, model_wrapper
         else:
             from .sampler.dpm_solver import DPM_Solver, NoiseScheduleVP, model_wrapper
-        if native:
+        if guided:
+            # one wrapper for both backends: NativeUNetModel is a plain callable (x, t_input, cond) around the UNet too.  The
+            # wrapper closes over this utterance's conditions, so it - and the solver around it - is rebuilt per call; the
+            # compiled plans (with their captured graphs) and the persistent buffers of the native handle are kept.
+            from .sampler._plan import NativeUNetModel
+            enc, mask, uenc, umask = self._guidance_conditions(refer, spec_lengths, negative_refer, negative_lengths)
+            cache = self.__dict__.setdefault("_native_samplers", {})
+            bkey = (self.betas.data_ptr(), self.betas._version, str(self.betas.device))
+            ent = cache.get((sample_method, "guided"))
+            if ent is None or ent["betas"] != bkey:
+                ent = cache[(sample_method, "guided")] = {"betas": bkey, "native": NativeUNetModel(self.diff_model.unet, content, enc, mask, umask),
+                                                          "schedule": NoiseScheduleVP(schedule="discrete", betas=self.betas), "plans": {}}
+            nm = ent["native"]
+            nm.cond, nm.enc, nm.mask, nm.uncond_mask = content, enc, mask, umask
+            model_fn = model_wrapper(nm, ent["schedule"], model_type="x_start", guidance_type="classifier-free", condition=enc,
+                                     unconditional_condition=uenc, guidance_scale=float(guidance_scale))
+            solver = (UniPC(model_fn, ent["schedule"], variant="bh2") if sample_method == "unipc"
+                      else DPM_Solver(model_fn, ent["schedule"], algorithm_type="dpmsolver++"))
+            solver._plans = ent["plans"]
+        elif native:
             # schedule, solver (with its compiled plan and captured hipGraph) and the native model handle are kept per
             # sampling method: a new utterance only swaps the conditioning; same-shape utterances replay the graph
             cache = self.__dict__.setdefault("_native_samplers", {})
@@ -383,9 +425,10 @@ class NaturalSpeech2(nn.Module):
 
     @torch.no_grad()
     def sample(self, text, spec, text_lengths, spec_lengths, tone, language, vocos, sampling_timesteps=200,
-               sample_method="unipc", noise=None, prior_noise=None):
+               sample_method="unipc", noise=None, prior_noise=None, guidance_scale=1.0, negative_refer=None, negative_lengths=None):
         """reference model3.py:1119-1203 (same positional signature).  `noise` = x_T, `prior_noise` = the prior's
-        normal draw (forwarded as `noise=` to this package's VITS.infer); both default to fresh torch.randn draws."""
+        normal draw (forwarded as `noise=` to this package's VITS.infer); both default to fresh torch.randn draws.
+        guidance_scale / negative_refer / negative_lengths: classifier-free guidance, see sample_from_prior."""
         self.sampling_timesteps = sampling_timesteps
         if not hasattr(self, "vits"):
             raise RuntimeError("NaturalSpeech2.sample needs the VITS prior: construct with vits=<module with .infer(...)> "
@@ -394,7 +437,8 @@ class NaturalSpeech2(nn.Module):
             content, refer = self.vits.infer(text, text_lengths, spec, spec_lengths, tone, language)
         else:
             content, refer = self.vits.infer(text, text_lengths, spec, spec_lengths, tone, language, noise=prior_noise)
-        return self.sample_from_prior(content, refer, text_lengths, spec_lengths, vocos, sample_method, noise)
+        return self.sample_from_prior(content, refer, text_lengths, spec_lengths, vocos, sample_method, noise,
+                                      guidance_scale, negative_refer, negative_lengths)
 
 
 # ---- SURVEY.md §8f rank 3 (inference side of the VITS prior, from the text encoder's outputs onward) ------------------

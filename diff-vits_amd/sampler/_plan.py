@@ -167,10 +167,19 @@ def wrap_model(model, noise_schedule, model_type="noise", model_kwargs={}, guida
         noise_uncond, noise = noise_pred_fn(x_in, t_in, cond=c_in).chunk(2)
         return noise_uncond + guidance_scale * (noise - noise_uncond)
 
-    # (the direct x0 route - and with it the native graph - is taken for the unguided wrapper only: a guided model_fn is an
-    # arbitrary noise prediction for the solvers)
+    # (the direct x0 route of the STEPPED loop - "call the raw model" - is the unguided wrapper's only: a guided model_fn is an
+    # arbitrary noise prediction for the solvers there)
     if guidance_type == "uncond":
         model_fn._dv = dict(model=model, model_type=model_type, model_kwargs=model_kwargs, noise_schedule=ns)
+    elif guidance_type == "classifier-free" and model_type == "x_start" and isinstance(model, NativeUNetModel):
+        # Classifier-free guidance is tensor arithmetic around the denoiser: a run that can be replayed as one graph keeps the
+        # guidance inside it (dv_plan_set_guidance; sample_with_plan decides).  Recorded under a name of its own: `_dv` means
+        # "the raw model IS the data prediction" to the stepped loop, which would drop the guidance (and the condition).
+        # guidance_scale == 1 or no unconditional condition: the reference evaluates once, with `condition` (:162-163) - the
+        # unguided graph with `condition` as the encoder states.
+        model_fn._dv_cfg = dict(model=model, model_type=model_type, model_kwargs=model_kwargs, noise_schedule=ns,
+                                condition=condition, unconditional_condition=unconditional_condition,
+                                guidance_scale=float(guidance_scale))
     return model_fn
 
 
@@ -178,10 +187,12 @@ class Plan:
     """Compiled multistep loop: events + fp64-derived coefficient rows.
     `thresholding=(ratio, max_val, mask)`: dynamic thresholding of the data prediction as part of the native loop
     (dv_plan_set_thresholding) - `mask` a tuple of nfe truth values, the evaluations it applies to (None: all).  It does not
-    change the tables: `run_python` takes it, like every correction, as its `x0_hook`."""
+    change the tables: `run_python` takes it, like every correction, as its `x0_hook`.
+    `guidance=scale`: classifier-free guidance as part of the native loop (dv_plan_set_guidance; None: off).  It does not
+    change the tables either: `run_python` evaluates whatever `data_model` it is given."""
 
     def __init__(self, solver, betas, steps, order, skip_type, lower_order_final, t_start=None, t_end=None,
-                 denoise_to_zero=False, schedule=("discrete", 0.0, 0.0), method="multistep", thresholding=None):
+                 denoise_to_zero=False, schedule=("discrete", 0.0, 0.0), method="multistep", thresholding=None, guidance=None):
         L = _lib()
         self.method = method
         for name, v in (("t_start", t_start), ("t_end", t_end)):
@@ -193,7 +204,8 @@ class Plan:
                              .format(skip_type))
         betas = np.ascontiguousarray(betas, dtype=np.float32)
         self._args = (solver, betas, steps, order, skip_type, lower_order_final, t_start, t_end, denoise_to_zero, schedule, method,
-                      thresholding)
+                      thresholding, None)
+        self._guided = {}             # guidance scale -> the guided sibling of this plan (with_guidance)
         self._per_shape = {}          # captured graphs live in the native plan, one per plan: a copy per input shape
         self._h = C.c_void_p()
         L.check(L.lib().dv_sampler_plan_method(solver, L.SCHEDULE[schedule[0]], betas.ctypes.data_as(C.c_void_p), len(betas),
@@ -225,6 +237,9 @@ class Plan:
         self.thresholding = None
         if thresholding is not None:
             self.set_thresholding(thresholding)
+        self.guidance = None
+        if guidance is not None:
+            self.set_guidance(guidance)
 
     def set_thresholding(self, thresholding):
         """(ratio, max_val, mask | None) switches the native loop's dynamic thresholding on, None off; either way the plan's
@@ -242,7 +257,40 @@ class Plan:
                 thresholding = (ratio, max_val, tuple(bool(v) for v in mask))
             L.check(L.lib().dv_plan_set_thresholding(self._h, float(ratio), float(max_val), buf), "dv_plan_set_thresholding")
         self.thresholding = thresholding
-        self._args = self._args[:11] + (thresholding,)
+        self._args = self._args[:11] + (thresholding,) + self._args[12:]
+        self._guided.clear()          # (the guided siblings were made with the old thresholding: with_guidance makes new ones)
+
+    def graph_nodes(self):
+        """Nodes (kernel launches) of the hipGraph this plan's last native run captured; 0 while it holds none."""
+        L = _lib()
+        n = C.c_int64()
+        L.check(L.lib().dv_plan_graph_nodes(self._h, C.byref(n)), "dv_plan_graph_nodes")
+        return n.value
+
+    def set_guidance(self, scale):
+        """A finite scale switches the native loop's classifier-free guidance on (dv_sampler_run then needs the engine at twice
+        the batch of x, conditioned with [unconditional | conditional]), None off; a change drops the plan's captured graph."""
+        L = _lib()
+        if scale is None:
+            L.check(L.lib().dv_plan_set_guidance(self._h, 1.0, 0), "dv_plan_set_guidance")
+        else:
+            scale = float(scale)
+            L.check(L.lib().dv_plan_set_guidance(self._h, scale, 1), "dv_plan_set_guidance")
+        self.guidance = scale
+        self._args = self._args[:12] + (scale,)
+
+    def with_guidance(self, scale):
+        """The guided sibling of this plan (same tables and thresholding, guidance `scale`): a plan of its own, so that guided
+        and unguided runs of one solver never share a handle or a graph; its for_shape copies carry the guidance.  It takes
+        the thresholding this plan has NOW (set_thresholding on this plan drops the siblings).  Siblings are kept for the 4
+        most recent scales: every new scale compiles a plan and its first run captures a graph, so a caller who sweeps
+        guidance_scale over more values than that pays the compile and the capture again each time."""
+        scale = float(scale)
+        if scale not in self._guided:
+            if len(self._guided) >= 4:                         # bounded: drop the oldest scale
+                del self._guided[next(iter(self._guided))]
+            self._guided[scale] = Plan(*self._args[:12], guidance=scale)
+        return self._guided[scale]
 
     def for_shape(self, shape):
         """The plan whose captured hipGraph belongs to inputs of this shape (this one for the first shape seen, a copy
@@ -340,15 +388,38 @@ class NativeUNetModel:
     solver path keeps working.  Holds this package's UNet (backend='hip'), the channel-concat
     condition `cond` [B, in-out, T] and the cross-attention inputs."""
 
-    def __init__(self, unet, cond, encoder_hidden_states, encoder_attention_mask=None):
+    def __init__(self, unet, cond, encoder_hidden_states, encoder_attention_mask=None, uncond_mask=None):
         self.unet, self.cond, self.enc, self.mask = unet, cond, encoder_hidden_states, encoder_attention_mask
+        self.uncond_mask = uncond_mask      # key mask of the unconditional half of a guided evaluation (None: `mask`)
 
-    def __call__(self, x, t_input, **kwargs):
-        sample = x if self.cond is None else torch.cat([x, self.cond], dim=1)
-        return self.unet(sample, t_input, self.enc, encoder_attention_mask=self.mask).sample
+    def _pair_mask(self):
+        """Key mask of a guided evaluation's 2B rows: [unconditional | conditional]."""
+        if self.mask is None and self.uncond_mask is None:
+            return None
+        cm = self.mask if self.mask is not None else torch.ones_like(self.uncond_mask)
+        um = self.uncond_mask if self.uncond_mask is not None else cm
+        return torch.cat([um.to(cm.dtype), cm])
 
-    def run_plan(self, plan, x):
+    def __call__(self, x, t_input, cond=None, **kwargs):
+        """`cond` (the reference's third positional argument, dpm_solver.py:284-287): encoder hidden states [n, L, D] in place
+        of the stored ones; n = twice the stored batch is a guided evaluation [unconditional | conditional]: the
+        channel-concat condition and the masks are repeated."""
+        if cond is None:
+            sample = x if self.cond is None else torch.cat([x, self.cond], dim=1)
+            return self.unet(sample, t_input, self.enc, encoder_attention_mask=self.mask).sample
+        cc, mask = self.cond, self.mask
+        if cond.shape[0] == 2 * self.enc.shape[0]:
+            cc = None if cc is None else torch.cat([cc, cc])
+            mask = self._pair_mask()
+        sample = x if cc is None else torch.cat([x, cc], dim=1)
+        return self.unet(sample, t_input, cond, encoder_attention_mask=mask).sample
+
+    def run_plan(self, plan, x, guidance=None):
         """hipGraph replay of the whole loop (dv_sampler_run).  Returns a new tensor.
+        `guidance` = the record model_wrapper left for a classifier-free wrapper (condition, unconditional_condition,
+        guidance_scale): with a scale other than 1 and an unconditional condition the engine runs at 2B rows on
+        [unconditional | conditional] and the plan's guided sibling combines the pair inside the graph; otherwise the unguided
+        graph runs with `condition` as the encoder states.
 
         Does not block the host in the steady state (engine.verify_handover_default(): "lazy").  While the engine's schedule
         uses in-launch hand-overs (the default on a GPU the process has to itself) the first run of a newly planned schedule is
@@ -357,19 +428,33 @@ class NativeUNetModel:
         run) or by `unet.hip_engine().wait()` (False).  DVITS_HANDOVER_VERIFY=eager restores one host wait per run."""
         L = _lib()
         eng = self.unet.hip_engine()
-        out = self._run_plan_once(plan, x, eng, L)
+        out = self._run_plan_once(plan, x, eng, L, guidance)
         # In-launch hand-overs need the device to themselves; on a shared GPU one may time out (bounded wait, flag in host
         # memory): the engine then drops to the fallback schedule and the run is repeated on it - degraded, not dead
         # (VERDICT r2 #6); when that check happens: UNetEngine.result_leaves
-        out2 = eng.result_leaves(lambda: self._run_plan_once(plan, x, eng, L))
+        out2 = eng.result_leaves(lambda: self._run_plan_once(plan, x, eng, L, guidance))
         return out if out2 is None else out2
 
-    def _run_plan_once(self, plan, x, eng, L):
+    def _run_plan_once(self, plan, x, eng, L, guidance=None):
         B, C_, T = x.shape
         eng.before_enqueue()             # (lazy verification: a run before a long host pause is verified here - engine.py)
-        eng.prepare(B, T, self.enc.shape[1])
-        bias = self.unet._bias_from_mask(self.mask, torch.float32)
-        eng.set_cond(self.enc, bias)
+        enc, mask, scale = self.enc, self.mask, None
+        if guidance is not None:
+            enc = guidance["condition"]
+            if enc is None:
+                raise ValueError("model_wrapper(guidance_type='classifier-free') needs `condition` (encoder hidden states "
+                                 "[B, L, D]); got None")
+            if guidance["guidance_scale"] != 1.0 and guidance["unconditional_condition"] is not None:
+                scale = guidance["guidance_scale"]
+                enc = torch.cat([guidance["unconditional_condition"].to(enc), enc])
+                mask = self._pair_mask()
+        if enc.shape[0] != (B if scale is None else 2 * B):
+            raise RuntimeError("condition batch %d does not match x batch %d" % (enc.shape[0] // (1 if scale is None else 2), B))
+        eng.prepare(B if scale is None else 2 * B, T, enc.shape[1])
+        bias = self.unet._bias_from_mask(mask, torch.float32)
+        eng.set_cond(enc, bias)
+        if scale is not None:
+            plan = plan.with_guidance(scale)
         # Persistent input / condition buffers per shape: the captured graph is keyed on their addresses (and on the
         # engine's schedule handle), so a new utterance of a shape seen before replays its graph instead of re-capturing
         # steps x ~160 launches.  (Bounded: the engine keeps DVITS_PLAN_CACHE schedules.)
@@ -400,8 +485,9 @@ def dynamic_thresholding(x0, ratio, max_val):
 
 def native_graph_model(model_fn, x):
     """The NativeUNetModel behind `model_fn` if a run on `x` can be replayed as one graph (this package's UNet on the HIP
-    engine, a CUDA tensor, no model kwargs), else None.  Corrections and intermediates are the caller's to rule out."""
-    info = getattr(model_fn, "_dv", None)
+    engine, a CUDA tensor, no model kwargs; unguided or classifier-free), else None.  Corrections and intermediates are the
+    caller's to rule out."""
+    info = getattr(model_fn, "_dv", None) or getattr(model_fn, "_dv_cfg", None)
     if info is None or info["model_type"] != "x_start":
         return None
     raw = info["model"]
@@ -417,6 +503,13 @@ def sample_with_plan(plan, model_fn, noise_schedule, x, intermediates=None, x0_h
     info = getattr(model_fn, "_dv", None)
     ns = noise_schedule
     B = x.shape[0]
+    cfg = getattr(model_fn, "_dv_cfg", None)
+    if (cfg is not None and intermediates is None and x0_hook is None and xt_hook is None
+            and native_graph_model(model_fn, x) is not None):
+        # a classifier-free wrapper goes native under the conditions of an unguided one; stepped it stays the generic noise
+        # prediction below (info is None)
+        with torch.no_grad():
+            return cfg["model"].run_plan(plan, x, guidance=cfg)
     with torch.no_grad():
         if info is not None and info["model_type"] == "x_start":
             raw = info["model"]

@@ -265,6 +265,24 @@ int dv_plan_set_thresholding(dv_plan* p, double ratio, double max_val, const uin
  * without thresholding. */
 int dv_sampler_run_custom_rows(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, int32_t rows, int64_t numel, void* stream);
 
+/* model_wrapper(guidance_type='classifier-free', condition=, unconditional_condition=, guidance_scale=) (dpm_solver.py:322-330,
+ * uni_pc.py:221-229) as part of the compiled loop.  on != 0: every evaluation of dv_sampler_run runs the network on [x | x]
+ * - the unet must be prepared at an EVEN batch 2B and conditioned (dv_unet_set_cond) with [unconditional | conditional]
+ * encoder states and mask biases, the unconditional half first; x_inout [B, C, T] and cond [B, in_channels-C, T] hold B rows
+ * (an odd unet batch: DV_ERR_INVALID before anything is launched) - and the history slot receives
+ * x0_u + scale * (x0_c - x0_u): d = x0_c - x0_u in float32, then fmaf(scale, d, x0_u).  (The reference combines the noise
+ * predictions; they are linear in x0, so this is the same guided prediction without the x0 -> noise -> x0 round trip.)
+ * Thresholding (dv_plan_set_thresholding), where the plan has it, sees the guided prediction, per row of x_inout.  The plan
+ * owns three 2B-row staging buffers (network input, network output, cond - the latter filled once per run); the cost per
+ * evaluation is two elementwise launches.  scale must be finite (DV_ERR_INVALID); on = 0 switches guidance off again (scale
+ * is ignored).  Any change drops the captured graph.  dv_sampler_run_custom / _rows refuse a guided plan (DV_ERR_INVALID):
+ * the callback has no pair of conditions. */
+int dv_plan_set_guidance(dv_plan* p, double scale, int32_t on);
+/* *n_nodes = nodes of the hipGraph the last dv_sampler_run of this plan captured (kernel launches of the complete loop:
+ * the head-of-loop chains, every evaluation, every update); 0 while the plan holds no graph (never run, dropped by a
+ * change, DVITS_NO_GRAPH=1).  For measurements and tests: what a captured loop really holds. */
+int dv_plan_graph_nodes(const dv_plan* p, int64_t* n_nodes);
+
 /* ---- prompt encoder: PromptEncoder.forward, reference model3.py:408-433 ------------------
  * The reference recomputes it inside every denoiser call (Diffusion_Encoder.forward, model3.py:902-906) although it
  * does not depend on the step; the host mirror calls this once per sampler run and feeds the result to
@@ -337,6 +355,14 @@ int dv_op_conv3(const float* x, const float* w, const float* bias, const float* 
  * DV_ERR_INVALID before anything is launched. */
 int dv_op_dynamic_threshold(float* x0_inout, int32_t rows, int64_t row_numel, double ratio, double max_val, float* s_out,
                             void* stream);
+/* The guidance combination on the kernel the sampler loop runs (k_cfg_combine): x0_pair [2 rows, row_numel] holds the
+ * unconditional predictions in rows 0 .. rows-1 and the conditional ones behind them; out [rows, row_numel] (no overlap with
+ * x0_pair) receives fmaf(scale, c - u, u) with the difference rounded to float32 first.  rows in 1..2048, row_numel < 2^31, any
+ * 4-byte aligned addresses; a non-finite scale or a bad size: DV_ERR_INVALID before anything is launched. */
+int dv_op_cfg_combine(const float* x0_pair, float* out, int32_t rows, int64_t row_numel, double scale, void* stream);
+/* The other guidance kernel (k_cfg_pair_in): out[0 .. numel) = out[numel .. 2 numel) = in[0 .. numel), no overlap, any
+ * 4-byte aligned addresses, 1 <= numel <= 2^40; DV_ERR_INVALID before anything is launched otherwise. */
+int dv_op_cfg_pair_in(const float* in, float* out, int64_t numel, void* stream);
 
 #ifdef __cplusplus
 }
