@@ -31,6 +31,11 @@ class PencCfg(C.Structure):
                 ("n_layers", C.c_int32), ("num_heads", C.c_int32), ("ffn_kernel", C.c_int32)]
 
 
+class TencCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_vocab", "n_tones", "n_languages", "hidden_channels", "filter_channels", "out_channels",
+                                         "n_heads", "n_layers", "kernel_size", "window_size", "gin_channels", "cond_layer_idx")]
+
+
 MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p)
 
 # every symbol include/dvits_hip.h declares: (restype, argtypes)
@@ -55,6 +60,14 @@ SIGNATURES = {
     "dv_penc_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_penc_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "dv_penc_probe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "dv_tenc_create": (C.c_int, [C.POINTER(TencCfg), C.POINTER(C.c_void_p)]),
+    "dv_tenc_destroy": (None, [C.c_void_p]),
+    "dv_tenc_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "dv_tenc_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "dv_tenc_forward": (C.c_int, [C.c_void_p] * 10),
+    "dv_tenc_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "dv_tenc_probe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "dv_op_rel_attention": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_unet_time_family": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32)]),
     "dv_unet_persist_ticks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]),

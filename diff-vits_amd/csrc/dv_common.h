@@ -304,6 +304,26 @@ struct AttnFragParams {
 };
 hipError_t launch_attention_frag(const AttnFragParams& p, hipStream_t st);
 
+// Self-attention with windowed relative-position key / value embeddings (k_rel_attention, kernels_relattn.hip; reference
+// attentions.py:142-300 as the text encoder uses it): per (utterance, head, 32-query block)
+//   s_ij = scale q_i . k_j + [|j - i| <= w] scale q_i . E_k[j - i + w],  p = softmax over the utterance's `lengths[b]` valid keys,
+//   o_i  = sum_j p_ij v_j + sum_{r = 0..2w, 0 <= i + r - w < length} p_{i, i + r - w} E_v[r]
+// q / k / v are fp32 rows (b * T + t) with head h at columns [h * d, h * d + d); E_k / E_v [2w + 1, d] are shared by the heads.
+// Query rows [length, T) are written as zeros.  d = 32, 64 or 128; T <= DV_RELATTN_MAX_T; w <= DV_RELATTN_MAX_WINDOW.
+enum { DV_RELATTN_MAX_T = 512, DV_RELATTN_MAX_WINDOW = 16 };
+struct RelAttnParams {
+  const float* q; const float* k; const float* v;
+  int ldq, ldk, ldv;
+  const float* emb_k; const float* emb_v;
+  const int64_t* lengths;        // [B] device: valid tokens per utterance (clamped to 0 .. T by the kernel)
+  float* o;                      // fp32 output [B * T, ldo] or null
+  bf16_t* o_hi; bf16_t* o_lo;    // split-plane output (the operand of conv_o) or null
+  int ldo;
+  int B, H, T, d, window;
+  float scale;                   // d^-1/2, or 1 when the q projection already carries it
+};
+hipError_t launch_rel_attention(const RelAttnParams& p, hipStream_t st);
+
 // ---------------------------------------------------------------------------------------
 // Persistent per-XCD schedule (persist.hip): operation table in device memory, executed by one launch.
 // ---------------------------------------------------------------------------------------

@@ -618,3 +618,120 @@ class PromptEncoderEngine:
         _lib.check(_lib.lib().dv_penc_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims),
                    "dv_penc_probe")
         return out
+
+
+class TextEncoderEngine:
+    """Native text encoder `enc_p` (dv_tenc_*, include/dvits_hip.h) for one mirror module (diff_vits_amd.model3.TextEncoder).
+    Weights are synced like PromptEncoderEngine's (re-packed when a parameter's data_ptr / _version moves); the planned
+    schedule is kept per (B, T): the handle holds one, a change of shape re-plans it (the packed weights survive)."""
+
+    def __init__(self, module):
+        self.module = module
+        enc = module.encoder
+        att = enc.attn_layers[0]
+        c = _lib.TencCfg()
+        c.n_vocab, c.n_tones, c.n_languages = module.emb.num_embeddings, module.tone_emb.num_embeddings, module.language_emb.num_embeddings
+        c.hidden_channels, c.out_channels = module.hidden_channels, module.out_channels
+        c.filter_channels, c.kernel_size = enc.ffn_layers[0].conv_1.out_channels, enc.ffn_layers[0].kernel_size
+        c.n_heads, c.n_layers, c.window_size = att.n_heads, enc.n_layers, att.window_size
+        c.gin_channels = enc.spk_emb_linear.in_features if hasattr(enc, "spk_emb_linear") else 0
+        c.cond_layer_idx = enc.cond_layer_idx if c.gin_channels else 0
+        self.cfg = c
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().dv_tenc_create(C.byref(c), C.byref(self._h)), "dv_tenc_create")
+        self._weight_sig = None
+        self._prepared = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                _lib.lib().dv_tenc_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def sync_weights(self):
+        m = self.module
+        sig = tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
+        if sig == self._weight_sig:
+            return
+        L = _lib.lib()
+        for name, t in m.state_dict().items():
+            if not t.is_cuda:
+                raise RuntimeError("backend='hip' needs the module on a GPU (parameter %s is on %s)" % (name, t.device))
+            t32 = t.detach().to(torch.float32).contiguous()
+            shape = (C.c_int64 * t32.dim())(*t32.shape)
+            _lib.check(L.dv_tenc_set_weight(self._h, name.encode(), _lib.ptr(t32), shape, t32.dim()), "dv_tenc_set_weight(%s)" % name)
+        torch.cuda.synchronize()
+        self._weight_sig = sig
+        self._prepared = None
+
+    def validate(self, ids, lengths, tone, language):
+        """The host checks of the mirror (one device-to-host read): ValueError before anything is launched."""
+        c = self.cfg
+        for name, t, n in (("x", ids, c.n_vocab), ("tone", tone, c.n_tones), ("language", language, c.n_languages)):
+            check_index_tensor(name, t, n, ids.shape)
+        check_lengths(lengths, ids.shape[0], ids.shape[1])
+
+    def forward(self, ids, lengths, tone, language, g=None, validate=True):
+        """ids, tone, language int64 [B, T], lengths int64 [B], g [B, gin] / [B, gin, 1] or None, all on the GPU ->
+        (x [B, H, T], m [B, C, T], logs [B, C, T]) float32, padding frames zero.  validate=False skips the host checks
+        (they read the device: not allowed while a graph is being captured)."""
+        for name, t in (("x", ids), ("x_lengths", lengths), ("tone", tone), ("language", language)) + ((("g", g),) if g is not None else ()):
+            if not t.is_cuda:
+                raise RuntimeError("text_encoder backend='hip' needs GPU tensors; got %s on %s" % (name, t.device))
+        if validate:
+            self.validate(ids, lengths, tone, language)
+        elif any(t.dtype != torch.int64 for t in (ids, lengths, tone, language)):
+            raise ValueError("x, x_lengths, tone and language must be int64")
+        self.sync_weights()
+        B, T = ids.shape
+        if (B, T) != self._prepared:
+            _lib.check(_lib.lib().dv_tenc_prepare(self._h, B, T, _lib.PREC_BF16X3), "dv_tenc_prepare")
+            self._prepared = (B, T)
+        c = self.cfg
+        gp = None
+        if g is not None:
+            if c.gin_channels == 0:
+                raise ValueError("this text encoder was built without speaker conditioning (gin_channels = 0)")
+            gp = g.detach().to(torch.float32).reshape(B, -1).contiguous()
+            if gp.shape[1] != c.gin_channels:
+                raise ValueError("g must hold %d channels per utterance, got %s" % (c.gin_channels, tuple(g.shape)))
+        ids, tone, language, lengths = (t.contiguous() for t in (ids, tone, language, lengths))
+        x = torch.empty((B, c.hidden_channels, T), device=ids.device, dtype=torch.float32)
+        stats = torch.empty((2, B, c.out_channels, T), device=ids.device, dtype=torch.float32)
+        _lib.check(_lib.lib().dv_tenc_forward(self._h, _lib.ptr(ids), _lib.ptr(tone), _lib.ptr(language), _lib.ptr(lengths), _lib.ptr(gp),
+                                              _lib.ptr(x), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.stream_ptr()), "dv_tenc_forward")
+        return x, stats[0], stats[1]
+
+    def stats(self):
+        n, f = C.c_int64(), C.c_double()
+        _lib.check(_lib.lib().dv_tenc_stats(self._h, C.byref(n), C.byref(f)), "dv_tenc_stats")
+        return n.value, f.value
+
+    def probe(self, name):
+        """Named intermediate [B, T, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1 at prepare time)."""
+        dims = (C.c_int64 * 3)()
+        _lib.check(_lib.lib().dv_tenc_probe(self._h, name.encode(), None, 0, dims), "dv_tenc_probe")
+        out = torch.empty(tuple(dims), dtype=torch.float32)
+        _lib.check(_lib.lib().dv_tenc_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims), "dv_tenc_probe")
+        return out
+
+
+def check_index_tensor(name, t, n, shape):
+    """int64, the expected shape, every entry in [0, n): ValueError otherwise (works on CPU and GPU tensors)."""
+    if t.dtype != torch.int64:
+        raise ValueError("%s must be int64, got %s" % (name, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+        raise ValueError("%s holds indices outside [0, %d)" % (name, n))
+
+
+def check_lengths(lengths, B, T):
+    if lengths.dtype != torch.int64:
+        raise ValueError("x_lengths must be int64, got %s" % lengths.dtype)
+    if tuple(lengths.shape) != (B,):
+        raise ValueError("x_lengths must have shape (%d,), got %s" % (B, tuple(lengths.shape)))
+    if int(lengths.min()) < 0 or int(lengths.max()) > T:
+        raise ValueError("x_lengths must lie in [0, %d]" % T)

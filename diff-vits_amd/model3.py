@@ -597,11 +597,16 @@ class Encoder(nn.Module):
 class TextEncoder(nn.Module):
     """reference model3.TextEncoder (model3.py:322-381).  The vocabulary sizes come from the reference's `text`
     package there (len(symbols), num_tones, num_languages = 108 / 11 / 3 in this checkout); here they are arguments.
-    Once per utterance over <= a few hundred tokens: plain torch ops on the caller's device."""
+    Once per utterance over <= a few hundred tokens: plain torch ops on the caller's device by default; backend='hip' (opt-in)
+    runs the whole forward on the native text-encoder engine (dv_tenc_*, csrc/tenc.hip) and fails loudly where it cannot."""
 
     def __init__(self, n_vocab, out_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size, p_dropout,
-                 gin_channels=0, n_tones=11, n_languages=3):
+                 gin_channels=0, n_tones=11, n_languages=3, backend=None):
         super().__init__()
+        if backend not in (None, "torch", "hip"):
+            raise ValueError("backend must be None, 'torch' or 'hip', got %r" % (backend,))
+        self.backend = backend                 # None / 'torch': the torch ops below; 'hip': the dv_tenc engine (opt-in)
+        self._engine = None
         self.out_channels, self.hidden_channels = out_channels, hidden_channels
         self.emb = nn.Embedding(n_vocab, hidden_channels)
         self.tone_emb = nn.Embedding(n_tones, hidden_channels)
@@ -611,7 +616,35 @@ class TextEncoder(nn.Module):
         self.encoder = Encoder(hidden_channels, filter_channels, n_heads, n_layers, kernel_size, p_dropout, gin_channels=gin_channels)
         self.proj = nn.Conv1d(hidden_channels, out_channels * 2, 1)
 
+    def hip_engine(self):
+        if self._engine is None:
+            from .engine import TextEncoderEngine
+            self._engine = TextEncoderEngine(self)
+        return self._engine
+
+    def _forward_hip(self, x, x_lengths, tone, language, g, validate=True):
+        """The native path: host checks (ValueError) before anything else, then GPU tensors or a RuntimeError - never a
+        fall-back to the torch ops."""
+        from .engine import check_index_tensor, check_lengths
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("backend='hip' is inference-only; construct with backend=None to train")
+        if validate:
+            if x.dim() != 2:
+                raise ValueError("x must be [B, T] token ids, got shape %s" % (tuple(x.shape),))
+            for name, t, n in (("x", x, self.emb.num_embeddings), ("tone", tone, self.tone_emb.num_embeddings),
+                               ("language", language, self.language_emb.num_embeddings)):
+                check_index_tensor(name, t, n, x.shape)
+            check_lengths(x_lengths, x.shape[0], x.shape[1])
+        for name, t in (("x", x), ("x_lengths", x_lengths), ("tone", tone), ("language", language)):
+            if not t.is_cuda:
+                raise RuntimeError("text encoder backend='hip' needs GPU tensors; got %s on %s" % (name, t.device))
+        xo, m, logs = self.hip_engine().forward(x, x_lengths, tone, language, g, validate=False)
+        x_mask = torch.unsqueeze(sequence_mask(x_lengths, x.size(1)), 1).to(xo.dtype)
+        return xo, m, logs, x_mask
+
     def forward(self, x, x_lengths, tone, language, g=None):
+        if self.backend == "hip":
+            return self._forward_hip(x, x_lengths, tone, language, g)
         x = (self.emb(x) + self.tone_emb(tone) + self.language_emb(language)) * math.sqrt(self.hidden_channels)
         x = torch.transpose(x, 1, -1)
         x_mask = torch.unsqueeze(sequence_mask(x_lengths, x.size(2)), 1).to(x.dtype)
@@ -635,7 +668,7 @@ class VITS(nn.Module):
 
     def __init__(self, n_vocab=None, spec_channels=None, inter_channels=128, hidden_channels=256, filter_channels=256,
                  n_heads=2, n_layers=6, kernel_size=3, p_dropout=0.1, gin_channels=256, enc_p=None, n_tones=11, n_languages=3,
-                 backend=None, **unused):
+                 backend=None, text_encoder_backend=None, **unused):
         super().__init__()
         from .unet1d.embeddings import TextTimeEmbedding
         self.inter_channels, self.hidden_channels, self.gin_channels = inter_channels, hidden_channels, gin_channels
@@ -643,7 +676,7 @@ class VITS(nn.Module):
             self.enc_p = enc_p
         elif n_vocab is not None:
             self.enc_p = TextEncoder(n_vocab, inter_channels, hidden_channels, filter_channels, n_heads, n_layers, kernel_size,
-                                     p_dropout, gin_channels, n_tones, n_languages)
+                                     p_dropout, gin_channels, n_tones, n_languages, backend=text_encoder_backend)
         self.dp = DurationPredictor_unet(hidden_channels, 256, 100, 3, 0.5, backend=backend)
         self.ref_enc = TextTimeEmbedding(100, gin_channels, 1)
         self.o_proj = PromptEncoder(inter_channels, hidden_channels, inter_channels, 6, 0.2, gin_channels=gin_channels,

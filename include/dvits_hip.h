@@ -71,9 +71,26 @@ typedef struct {
   int32_t ffn_kernel;             /* 9 */
 } dv_penc_cfg;
 
+/* TextEncoder constructor arguments (reference model3.py:322-358 over attentions.Encoder, attentions.py:37-68): the product
+ * is 256 hidden channels, 2 heads (head dim 128), 6 post-norm layers, k = 3 feed-forward convolutions, relative-position
+ * window 4, speaker vector added before layer 2. */
+typedef struct {
+  int32_t n_vocab, n_tones, n_languages;  /* rows of emb / tone_emb / language_emb */
+  int32_t hidden_channels;        /* H, a multiple of 32; H / n_heads must be 32, 64 or 128 */
+  int32_t filter_channels;        /* feed-forward width, a multiple of 32 */
+  int32_t out_channels;           /* C: proj writes 2C statistics channels (m | logs) */
+  int32_t n_heads;
+  int32_t n_layers;
+  int32_t kernel_size;            /* of conv_1 / conv_2, odd ('same' padding) */
+  int32_t window_size;            /* relative-position window w: emb_rel_k / emb_rel_v are [1, 2w+1, H / n_heads]; <= 16 */
+  int32_t gin_channels;           /* speaker vector width, 0 = no spk_emb_linear */
+  int32_t cond_layer_idx;         /* the layer in front of which the speaker vector is added */
+} dv_tenc_cfg;
+
 typedef struct dv_unet dv_unet;
 typedef struct dv_plan dv_plan;
 typedef struct dv_penc dv_penc;
+typedef struct dv_tenc dv_tenc;
 
 const char* dv_last_error(void);
 /* Library/version probe: returns e.g. "dvits_hip 0.1 gfx950". */
@@ -307,7 +324,40 @@ int dv_penc_stats(dv_penc* p, int64_t* n_launch, double* flops);
  * there, in the reference neither), "layerN" (the layer's output), "out_proj" (before the last LayerNorm). */
 int dv_penc_probe(dv_penc* p, const char* name, float* host_out, int64_t capacity, int64_t* dims);
 
+/* ---- text encoder enc_p: TextEncoder.forward, reference model3.py:360-381 (phoneme ids -> prior statistics) -------
+ * The contracts of the dv_penc_* functions.  Weights under their reference names relative to "enc_p.": "emb.weight",
+ * "tone_emb.weight", "language_emb.weight", "encoder.attn_layers.N.conv_{q,k,v,o}.{weight,bias}",
+ * "encoder.attn_layers.N.emb_rel_{k,v}", "encoder.norm_layers_{1,2}.N.{gamma,beta}", "encoder.ffn_layers.N.conv_{1,2}.{weight,bias}",
+ * "encoder.spk_emb_linear.{weight,bias}", "proj.{weight,bias}"; float32, in the reference's shapes, copied. */
+int dv_tenc_create(const dv_tenc_cfg* cfg, dv_tenc** out);
+void dv_tenc_destroy(dv_tenc* t);
+int dv_tenc_set_weight(dv_tenc* t, const char* name, const void* dev_ptr, const int64_t* shape, int32_t ndim);
+/* Packs the weights (once per weight set) and plans the launches for B utterances of T tokens (T <= 512, the largest length
+ * k_rel_attention is tested at: DV_ERR_INVALID beyond).  precision: DV_PREC_BF16X3; DV_PREC_BF16 is unsupported (DV_ERR_INVALID
+ * with a message). */
+int dv_tenc_prepare(dv_tenc* t, int32_t B, int32_t T, int32_t precision);
+/* ids, tone, language: DEVICE int64 [B, T] (indices outside their table are clamped into it, never read out of bounds: the caller
+ * validates); lengths: DEVICE int64 [B], valid tokens per utterance (values outside 0..T are clamped); g: [B, gin_channels] float32
+ * or NULL (no speaker conditioning in this call).  Outputs, channels-first as the reference returns them, padding frames
+ * exactly zero: x [B, H, T], m [B, C, T], logs [B, C, T].  Allocates nothing and never waits for the device: capturable into a
+ * graph. */
+int dv_tenc_forward(dv_tenc* t, const int64_t* ids, const int64_t* tone, const int64_t* language, const int64_t* lengths,
+                    const float* g, float* x, float* m, float* logs, void* stream);
+/* Launches one forward enqueues (the two speaker-conditioning launches included) and the FLOPs of its contractions. */
+int dv_tenc_stats(dv_tenc* t, int64_t* n_launch, double* flops);
+/* Probe, the contract of dv_penc_probe (channels-last [B, T, C], after a prepare with DVITS_KEEP_INTERMEDIATES=1).  Names: "emb",
+ * "layerN.attn" (after conv_o + residual, before LayerNorm 1), "layerN.ln1", "layerN.ffn1" (ReLU'd, masked conv_1 output, joined
+ * from its split planes), "layerN" (the layer's output), "proj" (2C statistics channels).  Padding rows hold zeros. */
+int dv_tenc_probe(dv_tenc* t, const char* name, float* host_out, int64_t capacity, int64_t* dims);
+
 /* ---- single-operator entry points (parity tests of each kernel through the C ABI) ---- */
+
+/* k_rel_attention alone: q, k, v, o float32 [B, T, H*d] (heads interleaved on the last axis), emb_k / emb_v [2*window+1, d] shared
+ * by the heads, lengths DEVICE int64 [B].  o_i = softmax_j over the utterance's valid keys of (q_i.k_j + [|j-i| <= window]
+ * q_i.emb_k[j-i+window]) / sqrt(d), times v_j, plus the in-range band probabilities times emb_v; rows >= lengths[b] are zeros.
+ * d = 32, 64 or 128; T <= 512; window <= 16; 16-byte aligned pointers.  DV_ERR_INVALID otherwise, before anything is launched. */
+int dv_op_rel_attention(const float* q, const float* k, const float* v, const float* emb_k, const float* emb_v,
+                        const int64_t* lengths, float* o, int32_t B, int32_t H, int32_t T, int32_t d, int32_t window, void* stream);
 
 /* y[B,Cout,T_out] = conv1d(act(x)) on channels-first tensors, through the implicit-GEMM
  * kernel: k = 1 or 3, stride 1/2, padding (k-1)/2, optional nearest upsample to `up_T`
