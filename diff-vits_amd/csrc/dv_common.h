@@ -467,3 +467,12 @@ hipError_t launch_dyn_thresh(float* x, int rows, int64_t n, float ratio, float m
 // 4-byte aligned addresses): out[0 .. n) = out[n .. 2 n) = in;  out[i] = fmaf(g, pair[n + i] - pair[i], pair[i]).  One launch each.
 hipError_t launch_cfg_pair_in(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_cfg_combine(const float* pair, float* out, int64_t n, float g, hipStream_t st);
+// length regulator of the VITS prior (kernels_regulate.hip): durations -> inclusive integer prefix sums cum [B, Tx] and frame counts
+// y_len [B] (-1: an utterance with a duration outside [0, 2^24] or a total beyond int32), then the aligned prior sample
+// z_p [B, C, Tp] = m_p[.., tok(t)] + (noise * expf(logs_p[.., tok(t)])) * noise_scale, tok(t) = first j < x_len with cum[j] > t (frames
+// without a token: m = logs = 0).  m_exp / logs_exp [B, C, Tp]: the gathered statistics, or null.  One launch each.
+hipError_t launch_dur_scan(const float* logw, const int64_t* x_lengths, int B, int Tx, float length_scale, int32_t* cum,
+                           int64_t* y_len, hipStream_t st);
+hipError_t launch_regulate_sample(const float* m_p, const float* logs_p, const int32_t* cum, const int64_t* x_lengths,
+                                  const float* noise, float noise_scale, int B, int C, int Tx, int Tp, float* z_p, float* m_exp,
+                                  float* logs_exp, hipStream_t st);

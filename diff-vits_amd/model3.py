@@ -663,14 +663,19 @@ class VITS(nn.Module):
     names) is built too; otherwise pass any module with the reference signature
     `enc_p(x, x_lengths, tone, language, g) -> (x, m_p, logs_p, x_mask)`, or call `infer_from_encoder`.  The duration
     predictor's UNet and `o_proj` run on the HIP engine (backend='hip'); the once-per-utterance glue (reference encoder,
-    alignment path, gathers) is a handful of torch ops on the same device.  `noise=` fixes the prior noise (the reference
-    draws torch.randn_like)."""
+    alignment path, gathers) is a handful of torch ops on the same device, or with prior_backend='hip' (opt-in) the native
+    length regulator (dv_op_regulate_*, csrc/kernels_regulate.hip: GPU tensors only, never a fall-back).  `noise=` fixes the
+    prior noise (the reference draws torch.randn_like)."""
 
     def __init__(self, n_vocab=None, spec_channels=None, inter_channels=128, hidden_channels=256, filter_channels=256,
                  n_heads=2, n_layers=6, kernel_size=3, p_dropout=0.1, gin_channels=256, enc_p=None, n_tones=11, n_languages=3,
-                 backend=None, text_encoder_backend=None, **unused):
+                 backend=None, text_encoder_backend=None, prior_backend=None, **unused):
         super().__init__()
         from .unet1d.embeddings import TextTimeEmbedding
+        if prior_backend not in (None, "hip"):
+            raise ValueError("prior_backend must be None or 'hip', got %r" % (prior_backend,))
+        self.prior_backend = prior_backend     # None: the torch ops of infer_from_encoder; 'hip': dv_op_regulate_* (opt-in)
+        self.native_regulator_calls = 0        # how often the native length regulator ran (tests tell the paths apart by it)
         self.inter_channels, self.hidden_channels, self.gin_channels = inter_channels, hidden_channels, gin_channels
         if enc_p is not None:
             self.enc_p = enc_p
@@ -688,17 +693,58 @@ class VITS(nn.Module):
         """reference model3.py:839-860 (after the `enc_p` call).  Returns (z [B, inter, T'], y, y_lengths')."""
         if g is None:
             g = self.ref_enc(y.transpose(1, 2)).unsqueeze(-1)
+        if self.prior_backend == "hip":
+            for name, t in (("x", x), ("m_p", m_p), ("logs_p", logs_p), ("x_lengths", x_lengths), ("y", y)):
+                if not t.is_cuda:
+                    raise RuntimeError("prior_backend='hip' needs GPU tensors; got %s on %s" % (name, t.device))
         logw = self.dp(x, x_lengths, y, y_lengths)
-        w = torch.exp(logw) * x_mask * length_scale
-        w_ceil = torch.ceil(w)
-        y_len = torch.clamp_min(torch.sum(w_ceil, [1, 2]), 1).long()
-        y_mask = torch.unsqueeze(sequence_mask(y_len, None), 1).to(x_mask.dtype)
-        attn = generate_path(w_ceil, torch.unsqueeze(x_mask, 2) * torch.unsqueeze(y_mask, -1))
-        m_p = torch.matmul(attn.squeeze(1), m_p.transpose(1, 2)).transpose(1, 2)
-        logs_p = torch.matmul(attn.squeeze(1), logs_p.transpose(1, 2)).transpose(1, 2)
-        eps = torch.randn_like(m_p) if noise is None else noise.to(m_p)
-        z_p = m_p + eps * torch.exp(logs_p) * noise_scale
+        if self.prior_backend == "hip":
+            z_p, y_len = self._regulate_hip(logw, m_p, logs_p, x_lengths, noise_scale, length_scale, noise)
+        else:
+            w = torch.exp(logw) * x_mask * length_scale
+            w_ceil = torch.ceil(w)
+            y_len = torch.clamp_min(torch.sum(w_ceil, [1, 2]), 1).long()
+            y_mask = torch.unsqueeze(sequence_mask(y_len, None), 1).to(x_mask.dtype)
+            attn = generate_path(w_ceil, torch.unsqueeze(x_mask, 2) * torch.unsqueeze(y_mask, -1))
+            m_p = torch.matmul(attn.squeeze(1), m_p.transpose(1, 2)).transpose(1, 2)
+            logs_p = torch.matmul(attn.squeeze(1), logs_p.transpose(1, 2)).transpose(1, 2)
+            eps = torch.randn_like(m_p) if noise is None else noise.to(m_p)
+            z_p = m_p + eps * torch.exp(logs_p) * noise_scale
         return self.o_proj(z_p, y_len, g), y, y_len
+
+    def _regulate_hip(self, logw, m_p, logs_p, x_lengths, noise_scale, length_scale, noise):
+        """The native length regulator (csrc/kernels_regulate.hip): durations -> integer prefix sums and frame counts
+        (dv_op_regulate_lengths), one read of the frame counts, the aligned prior sample (dv_op_regulate_sample).  Returns
+        (z_p [B, C, T'], y_len int64 [B]); an utterance whose durations are not finite or exceed 2^24 frames is a ValueError."""
+        from . import _lib
+        B, C, Tx = m_p.shape
+        dev = m_p.device
+        logw32 = logw.detach().to(torch.float32).reshape(B, Tx).contiguous()
+        m32, logs32 = (t.detach().to(torch.float32).contiguous() for t in (m_p, logs_p))
+        xl = x_lengths.to(device=dev, dtype=torch.int64).contiguous()
+        cum = torch.empty((B, Tx), device=dev, dtype=torch.int32)
+        y_len = torch.empty((B,), device=dev, dtype=torch.int64)
+        L = _lib.lib()
+        _lib.check(L.dv_op_regulate_lengths(_lib.ptr(logw32), _lib.ptr(xl), B, Tx, float(length_scale), _lib.ptr(cum), _lib.ptr(y_len),
+                                            _lib.stream_ptr()), "dv_op_regulate_lengths")
+        counts = y_len.tolist()                # the one device-to-host read (the torch path has it in sequence_mask(y_len, None))
+        bad = [b for b, n in enumerate(counts) if n < 1]
+        if bad:
+            raise ValueError("utterance %d: a predicted duration is not finite or exceeds 2^24 frames" % bad[0])
+        Tp = max(counts)
+        if noise is None:
+            eps = torch.randn((B, C, Tp), device=dev, dtype=torch.float32)
+        else:
+            if tuple(noise.shape) != (B, C, Tp):
+                raise ValueError("noise must be %s (B, inter_channels, max frame count), got %s" % ((B, C, Tp), tuple(noise.shape)))
+            if not noise.is_cuda:
+                raise RuntimeError("prior_backend='hip' needs GPU tensors; got noise on %s" % (noise.device,))
+            eps = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+        z_p = torch.empty((B, C, Tp), device=dev, dtype=torch.float32)
+        _lib.check(L.dv_op_regulate_sample(_lib.ptr(m32), _lib.ptr(logs32), _lib.ptr(cum), _lib.ptr(xl), _lib.ptr(eps), float(noise_scale),
+                                           B, C, Tx, Tp, _lib.ptr(z_p), None, None, _lib.stream_ptr()), "dv_op_regulate_sample")
+        self.native_regulator_calls += 1
+        return z_p.to(m_p.dtype), y_len
 
     @torch.no_grad()
     def infer(self, x, x_lengths, y, y_lengths, tone, language, noise_scale=0.667, length_scale=1, noise_scale_w=0.8,

@@ -20,9 +20,10 @@ from .model3 import VITS, NaturalSpeech2
 TRAINING_ONLY_PREFIXES = ("vits.enc_q.",)
 
 
-def build_model(cfg, n_vocab, backend=None, text_encoder_backend=None):
+def build_model(cfg, n_vocab, backend=None, text_encoder_backend=None, prior_backend=None):
     """NaturalSpeech2(cfg) as model3.py:955-975 builds it: VITS(len(symbols), window_size // 2 + 1, **cfg['vits'])."""
-    vits = VITS(n_vocab, cfg["data"]["window_size"] // 2 + 1, backend=backend, text_encoder_backend=text_encoder_backend, **cfg["vits"])
+    vits = VITS(n_vocab, cfg["data"]["window_size"] // 2 + 1, backend=backend, text_encoder_backend=text_encoder_backend,
+                prior_backend=prior_backend, **cfg["vits"])
     return NaturalSpeech2(cfg, vits=vits, backend=backend)
 
 

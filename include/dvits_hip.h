@@ -359,6 +359,25 @@ int dv_tenc_probe(dv_tenc* t, const char* name, float* host_out, int64_t capacit
 int dv_op_rel_attention(const float* q, const float* k, const float* v, const float* emb_k, const float* emb_v,
                         const int64_t* lengths, float* o, int32_t B, int32_t H, int32_t T, int32_t d, int32_t window, void* stream);
 
+/* Length regulator of the prior at inference (reference model3.py:840-856), first half (k_dur_scan): logw float32 [B, Tx] (the
+ * duration predictor's output), x_lengths DEVICE int64 [B] (clamped to 0..Tx).  w = expf(logw) * [j < x_lengths[b]] * length_scale
+ * in float32, cum [B, Tx] int32 = inclusive prefix sums of ceil(w), y_len [B] int64 = max(cum[b, x_lengths[b] - 1], 1).  An utterance
+ * with a w that is NaN, infinite, negative or above 2^24, or whose total leaves int32, gets y_len[b] = -1 (its cum row is then
+ * unspecified; the other rows are unaffected): a value for the caller to check, not a fault.  length_scale must be finite and
+ * >= 0.  Null pointers or B, Tx < 1: DV_ERR_INVALID before anything is launched.  One launch, no allocation, no wait: capturable. */
+int dv_op_regulate_lengths(const float* logw, const int64_t* x_lengths, int32_t B, int32_t Tx, double length_scale, int32_t* cum,
+                           int64_t* y_len, void* stream);
+/* Second half (k_regulate_sample): m_p, logs_p float32 [B, C, Tx], cum as written above, noise float32 [B, C, Tp] ->
+ * z_p [B, C, Tp] = m_p[b, c, tok] + (noise[b, c, t] * expf(logs_p[b, c, tok])) * noise_scale, each product and the sum rounded to
+ * float32 in that order, tok = the first j < x_lengths[b] with cum[b, j] > t.  A frame without such a token (the padding behind an
+ * utterance's frames up to Tp, the single frame of an utterance of zero durations) takes m = logs = 0 as the reference's all-zero
+ * alignment row gives them: z_p = noise * noise_scale there.  m_p_exp / logs_p_exp [B, C, Tp] (or NULL) receive the gathered
+ * statistics.  Tp is the caller's (max(y_len) in the product).  Null pointers (other than the two optional outputs), B, C, Tx or
+ * Tp < 1, B > 65535: DV_ERR_INVALID before anything is launched.  One launch, no allocation, no wait: capturable. */
+int dv_op_regulate_sample(const float* m_p, const float* logs_p, const int32_t* cum, const int64_t* x_lengths, const float* noise,
+                          double noise_scale, int32_t B, int32_t C, int32_t Tx, int32_t Tp, float* z_p, float* m_p_exp,
+                          float* logs_p_exp, void* stream);
+
 /* y[B,Cout,T_out] = conv1d(act(x)) on channels-first tensors, through the implicit-GEMM
  * kernel: k = 1 or 3, stride 1/2, padding (k-1)/2, optional nearest upsample to `up_T`
  * frames first (0 = none).  w: [Cout, Cin, k] float32, bias [Cout] or NULL. */
