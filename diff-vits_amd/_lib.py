@@ -48,6 +48,13 @@ SIGNATURES = {
     "dv_unet_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dv_unet_set_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dv_unet_cond_signature": (C.c_uint64, [C.c_void_p]),
+    "dv_voice_capture": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
+    "dv_unet_bind_voices": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
+    "dv_unet_cond_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32]),
+    "dv_voice_signature": (C.c_uint64, [C.c_void_p]),
+    "dv_voice_bytes": (C.c_int64, [C.c_void_p]),
+    "dv_voice_destroy": (None, [C.c_void_p]),
     "dv_unet_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "dv_unet_forward_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int32]),

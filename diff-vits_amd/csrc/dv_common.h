@@ -476,3 +476,15 @@ hipError_t launch_dur_scan(const float* logw, const int64_t* x_lengths, int B, i
 hipError_t launch_regulate_sample(const float* m_p, const float* logs_p, const int32_t* cum, const int64_t* x_lengths,
                                   const float* noise, float noise_scale, int B, int C, int Tx, int Tp, float* z_p, float* m_exp,
                                   float* logs_exp, hipStream_t st);
+// k_gemm instantiation launch_gemm picks for a plain GEMM: BM | BN << 8 | BK << 16 | k-groups << 24 (kernels_gemm.hip)
+int gemm_variant(const GemmParams& p);
+// enrolled voices (kernels_voice.hip): one batch row of every conditioning segment <-> a voice record.  segs_dev: the device copy
+// of the segment table (sorted by chunk0; a segment of `bytes` per utterance owns ceil(bytes / 16) chunks of the record), chunks:
+// 16-byte chunks of one record; rows / recs: HOST arrays of n (batch row, record address) pairs - they travel in the launch's
+// argument block.  One launch per call up to DV_VOICE_MAX_ROWS rows, no allocation, no wait: capturable.  The caller checks the rows.
+struct VoiceSeg { char* base; uint32_t bytes; uint32_t chunk0; };
+constexpr int DV_VOICE_MAX_ROWS = 192;
+hipError_t launch_voice_gather(const VoiceSeg* segs_dev, int nseg, uint32_t chunks, const int32_t* rows, void* const* recs, int n,
+                               hipStream_t st);
+hipError_t launch_voice_scatter(const VoiceSeg* segs_dev, int nseg, uint32_t chunks, const int32_t* rows, void* const* recs, int n,
+                                hipStream_t st);

@@ -8,6 +8,7 @@
 #include "../../include/dvits_hip.h"
 #include "dv_common.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -17,6 +18,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -219,6 +221,16 @@ struct dv_unet {
     float* tsin = nullptr; float* h1 = nullptr; float* emb = nullptr; float* tproj_all = nullptr; int rows_cap = 0;
   } temb;
   int64_t generation = 0;
+  // Conditioning segment table (enrolled voices, below): every persistent buffer the cond schedule writes and the step schedule
+  // reads, utterance-major - kind 1 pooled-text row, 2 mask bias, 3 key bias, 4 fp32 K | V of block idx, 5..8 its K hi / K lo /
+  // V^T hi / V^T lo fragments.  row_cond[b]: row b has been conditioned since prepare (set_cond: all rows; a bind: its rows).
+  struct CondSeg { int kind, idx; char* base; size_t bytes; };
+  std::vector<CondSeg> cond_segs;
+  VoiceSeg* cond_segs_dev = nullptr;         // (in `owned`)
+  uint32_t cond_chunks = 0;                  // 16-byte chunks of one voice record
+  uint64_t cond_sig = 0;                     // layout signature (cond_signature)
+  std::vector<uint8_t> row_cond;
+  std::vector<const GemmParams*> cond_gemms; // the cond schedule's GEMMs (in gemm_store): their tile choice enters the signature
 };
 
 static void unet_release_packed(dv_unet* u) {
@@ -242,6 +254,7 @@ static void unet_release_prepared(dv_unet* u, bool keep_packed = false) {
   u->step_ops.clear(); u->cond_ops.clear(); u->probes.clear(); u->step_meta.clear(); u->gemm_store.clear();
   u->pops.clear(); u->step_pop.clear(); u->pops_dev = nullptr; u->psync = nullptr; u->persist_on = false; u->p_begin = u->p_end = 0;
   u->prepared = false; u->cond_set = false; u->flops = 0;
+  u->cond_segs.clear(); u->cond_segs_dev = nullptr; u->cond_chunks = 0; u->cond_sig = 0; u->row_cond.clear(); u->cond_gemms.clear();
 }
 
 // ----------------------------------------------------------------------------- C ABI: lifetime
@@ -804,6 +817,7 @@ struct Builder {
       u->gemm_store.emplace_back(new GemmParams(g));
       const GemmParams* gp = u->gemm_store.back().get();
       cur_gp = gp;
+      if (&ops == &u->cond_ops) u->cond_gemms.push_back(gp);
       dv_unet* uu = u;
       emit(ops, [gp, p, uu](hipStream_t st) {
         if (!uu->io.tp_base || !gp->gnx.xchg || !gp->gnx.tscale) return launch_gemm(*gp, p, st);
@@ -1006,6 +1020,7 @@ struct Builder {
 
   // cross-attention K/V of every transformer block (filled by the cond schedule)
   std::map<std::string, float*> cross_kv;
+  std::set<std::string> kv_read;   // blocks whose step operations read the fp32 K | V (and the mask bias) instead of fragments
   float* mask_bias = nullptr;    // [B, L]
   // the same as MFMA fragments for the blocks whose cross attention runs inside the chain kernel (kernels_chain.hip)
   struct XFrag { bf16_t* kf_hi = nullptr; bf16_t* kf_lo = nullptr; bf16_t* vf_hi = nullptr; bf16_t* vf_lo = nullptr; };
@@ -1337,7 +1352,7 @@ struct Builder {
     float* kv = cross_kv[b.p];
     Planes ao;
     if (attn_frag_on && !arena.exact && cross_frag.count(b.p)) ao = cross_attention_frag(ops, b.p, q2, Tp, C);
-    else ao = attention(ops, q2, C, kv, kv + C, 2 * C, mask_bias, Tp, L, C);
+    else { ao = attention(ops, q2, C, kv, kv + C, 2 * C, mask_bias, Tp, L, C); kv_read.insert(b.p); }
     release(q2);
     float* h3 = alloc((size_t)M * C);
     {
@@ -1864,6 +1879,29 @@ struct Builder {
       release_act(h);
     }
     if (!err.empty()) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
+    if (!dry) {
+      // conditioning segment table: what the cond schedule leaves behind for the step schedule, per utterance (dv_unet::CondSeg).
+      // The fp32 K | V of a block and the mask bias count only where a step operation reads them (kv_read); fragments
+      // wherever they exist.
+      const int H = c.num_heads, nT = (L + 31) / 32;
+      auto add = [&](int kind, int idx, const void* base, size_t bytes) {
+        u->cond_segs.push_back(dv_unet::CondSeg{kind, idx, const_cast<char*>(static_cast<const char*>(base)), bytes});
+      };
+      add(1, 0, aug_emb, (size_t)E * 4);
+      if (!kv_read.empty()) add(2, 0, mask_bias, (size_t)L * 4);
+      if (!cross_frag.empty()) add(3, 0, xbias, (size_t)nT * 32 * 4);
+      for (int i = 0; i < (int)xformers.size(); ++i) {
+        const std::string& p = xformers[i].first;
+        const int C = xformers[i].second;
+        if (kv_read.count(p)) add(4, i, cross_kv[p], (size_t)L * 2 * C * 4);
+        if (cross_frag.count(p)) {
+          const XFrag& xf = cross_frag[p];
+          const int d = C / H, KSq = d / 16, NBv = (d + 31) / 32;
+          const size_t kb = (size_t)H * nT * KSq * 64 * 8 * sizeof(bf16_t), vb = (size_t)H * nT * 2 * NBv * 64 * 8 * sizeof(bf16_t);
+          add(5, i, xf.kf_hi, kb); add(6, i, xf.kf_lo, kb); add(7, i, xf.vf_hi, vb); add(8, i, xf.vf_lo, vb);
+        }
+      }
+    }
     return DV_OK;
   }
 
@@ -2021,6 +2059,7 @@ struct Builder {
   }
 };
 
+static int cond_table_finish(dv_unet* u);   // (enrolled voices, below)
 extern "C" int dv_unet_prepare(dv_unet* u, int32_t B, int32_t T, int32_t L, int32_t precision, int32_t force_upsample_size) {
   if (!u) return dv_fail(DV_ERR_INVALID, "dv_unet_prepare: null handle");
   if (B <= 0 || T <= 0 || L <= 0) return dv_fail(DV_ERR_INVALID, "dv_unet_prepare: B, T, L must be positive");
@@ -2097,6 +2136,7 @@ extern "C" int dv_unet_prepare(dv_unet* u, int32_t B, int32_t T, int32_t L, int3
       u->p_begin = best0; u->p_end = best1; u->persist_on = true;
     }
   }
+  if (int rc = cond_table_finish(u)) { unet_release_prepared(u); return rc; }
   HIPCHK(hipDeviceSynchronize());
   u->prepared = true;
   u->weights_dirty = false;
@@ -2212,8 +2252,137 @@ extern "C" int dv_unet_set_cond(dv_unet* u, const float* enc, const float* mask_
   if (!u->prepared) return dv_fail(DV_ERR_STATE, "dv_unet_set_cond before dv_unet_prepare");
   u->io.enc = enc; u->io.mask = mask_bias;
   int rc = run_ops(u->cond_ops, (hipStream_t)stream, "set_cond");
-  if (rc == DV_OK) u->cond_set = true;
+  if (rc == DV_OK) { u->cond_set = true; std::fill(u->row_cond.begin(), u->row_cond.end(), (uint8_t)1); }
   return rc;
+}
+
+// ----------------------------------------------------------------------------- C ABI: enrolled voices
+// A voice record = one batch row of every conditioning segment (dv_unet::cond_segs, recorded by Builder::build), in its own
+// device allocation: it outlives the schedule it was taken from and binds to any schedule with the same layout signature.
+struct dv_voice { void* rec = nullptr; size_t bytes = 0; uint64_t sig = 0; };
+
+// FNV-1a over what fixes the layout and the meaning of a record: the engine configuration, the precision, L, every
+// segment's kind / block index / bytes per utterance, and the kernel instantiation of every cond GEMM.  B and T do not enter
+// by themselves: a segment is utterance-major, and which blocks keep which form of K / V is recorded by the segments.
+static uint64_t cond_signature(const dv_unet* u) {
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&h](const void* p, size_t n) { for (size_t i = 0; i < n; ++i) { h ^= static_cast<const unsigned char*>(p)[i]; h *= 1099511628211ull; } };
+  auto mix_i = [&](int64_t v) { mix(&v, sizeof(v)); };
+  const dv_unet_cfg& c = u->cfg;
+  mix_i(1);                                  // record format
+  mix_i(c.in_channels); mix_i(c.out_channels); mix_i(c.n_levels);
+  for (int i = 0; i < 6; ++i) mix_i(i < c.n_levels ? c.block_out_channels[i] : 0);
+  mix_i(c.layers_per_block); mix_i(c.num_heads); mix_i(c.cross_attention_dim); mix_i(c.norm_num_groups); mix_i(c.add_embed_heads);
+  mix(&c.norm_eps, sizeof(c.norm_eps));
+  mix_i(u->precision); mix_i(u->L); mix_i((int64_t)u->cond_segs.size());
+  for (const dv_unet::CondSeg& s : u->cond_segs) { mix_i(s.kind); mix_i(s.idx); mix_i((int64_t)s.bytes); }
+  // ... and how the bytes were ROUNDED: the K / V projections (and the pooled-text k | v) are GEMMs over M = B x L rows whose tile
+  // the launcher picks from the tile counts, the tuner or DVITS_GEMM_CFG, and tiles with another k-depth or k-group count sum a dot
+  // product in another order.  Two schedules share records only while every cond GEMM runs the same instantiation.
+  for (const GemmParams* g : u->cond_gemms) { mix_i(gemm_variant(*g)); mix_i(g->sk_buf ? g->sk_split : 0); }
+  return h ? h : 1;                          // (0 = "no schedule")
+}
+
+// Called at the end of dv_unet_prepare: record offsets (every segment starts on a 16-byte chunk of the record; a segment whose
+// bytes per utterance are no multiple of 16 is padded there, never in the buffer), the device copy of the table, the signature.
+static int cond_table_finish(dv_unet* u) {
+  u->cond_chunks = 0; u->cond_sig = 0; u->cond_segs_dev = nullptr;
+  u->row_cond.assign((size_t)u->B, 0);
+  if (u->cond_segs.empty()) return DV_OK;
+  std::vector<VoiceSeg> tab;
+  uint64_t chunk = 0;
+  for (const dv_unet::CondSeg& s : u->cond_segs) {
+    if (!s.base || s.bytes == 0 || s.bytes % 4 != 0 || s.bytes >= ((uint64_t)1 << 32) || ((uintptr_t)s.base & 255u))   // (arena blocks are 256-byte aligned)
+      return dv_fail(DV_ERR_INVALID, "conditioning segment kind %d block %d: %zu bytes per utterance cannot be recorded", s.kind, s.idx, s.bytes);
+    if ((uintptr_t)s.base < (uintptr_t)u->slab || (uintptr_t)s.base + (uint64_t)u->B * s.bytes > (uintptr_t)u->slab + u->slab_bytes)
+      return dv_fail(DV_ERR_INVALID, "conditioning segment kind %d block %d lies outside the arena", s.kind, s.idx);
+    tab.push_back(VoiceSeg{s.base, (uint32_t)s.bytes, (uint32_t)chunk});
+    chunk += (s.bytes + 15) / 16;
+  }
+  if (chunk >= ((uint64_t)1 << 31)) return dv_fail(DV_ERR_INVALID, "a voice record of %llu chunks is too large", (unsigned long long)chunk);
+  HIPCHK(hipMalloc((void**)&u->cond_segs_dev, tab.size() * sizeof(VoiceSeg)));
+  u->owned.push_back(u->cond_segs_dev);
+  HIPCHK(hipMemcpy(u->cond_segs_dev, tab.data(), tab.size() * sizeof(VoiceSeg), hipMemcpyHostToDevice));
+  u->cond_chunks = (uint32_t)chunk;
+  u->cond_sig = cond_signature(u);
+  return DV_OK;
+}
+
+static int voice_rows_ok(const dv_unet* u, const int32_t* rows, int32_t n, bool distinct, const char* what) {
+  std::vector<uint8_t> seen((size_t)u->B, 0);
+  for (int i = 0; i < n; ++i) {
+    if (rows[i] < 0 || rows[i] >= u->B) return dv_fail(DV_ERR_INVALID, "%s: row %d (entry %d) is outside the schedule's batch of %d", what, rows[i], i, u->B);
+    if (distinct && seen[rows[i]]) return dv_fail(DV_ERR_INVALID, "%s: row %d is named twice (entry %d)", what, rows[i], i);
+    seen[rows[i]] = 1;
+  }
+  return DV_OK;
+}
+
+extern "C" int dv_unet_cond_rows(dv_unet* u, uint8_t* flags, int32_t n, int32_t set) {
+  if (!u || !flags) return dv_fail(DV_ERR_INVALID, "dv_unet_cond_rows: null argument");
+  if (!u->prepared || !u->cond_chunks) return dv_fail(DV_ERR_STATE, "dv_unet_cond_rows before dv_unet_prepare");
+  if (n != u->B) return dv_fail(DV_ERR_INVALID, "dv_unet_cond_rows: %d flags for a batch of %d", n, u->B);
+  if (!set) { for (int i = 0; i < n; ++i) flags[i] = u->row_cond[i]; return DV_OK; }
+  bool all = true;
+  for (int i = 0; i < n; ++i) { u->row_cond[i] = flags[i] != 0; all = all && flags[i] != 0; }
+  u->cond_set = all;
+  return DV_OK;
+}
+
+extern "C" uint64_t dv_unet_cond_signature(const dv_unet* u) { return u && u->prepared ? u->cond_sig : 0; }
+extern "C" uint64_t dv_voice_signature(const dv_voice* v) { return v ? v->sig : 0; }
+extern "C" int64_t dv_voice_bytes(const dv_voice* v) { return v ? (int64_t)v->bytes : 0; }
+extern "C" void dv_voice_destroy(dv_voice* v) {
+  if (!v) return;
+  if (v->rec) (void)hipFree(v->rec);         // (hipFree waits for the device: a bind that still reads the record completes first)
+  delete v;
+}
+
+extern "C" int dv_voice_capture(dv_unet* u, const int32_t* rows, int32_t n, dv_voice** out) {
+  if (!u || !rows || !out || n < 1) return dv_fail(DV_ERR_INVALID, "dv_voice_capture: bad argument");
+  if (!u->prepared || !u->cond_chunks) return dv_fail(DV_ERR_STATE, "dv_voice_capture before dv_unet_prepare");
+  if (int rc = voice_rows_ok(u, rows, n, false, "dv_voice_capture")) return rc;
+  for (int i = 0; i < n; ++i)
+    if (!u->row_cond[rows[i]]) return dv_fail(DV_ERR_STATE, "dv_voice_capture: row %d has not been conditioned since dv_unet_prepare", rows[i]);
+  const size_t bytes = (size_t)u->cond_chunks * 16;
+  std::vector<dv_voice*> vs;
+  std::vector<void*> recs;
+  auto drop = [&] { for (dv_voice* v : vs) dv_voice_destroy(v); };
+  for (int i = 0; i < n; ++i) {
+    dv_voice* v = new dv_voice();
+    vs.push_back(v);
+    if (hipMalloc(&v->rec, bytes) != hipSuccess) { drop(); return dv_fail(DV_ERR_HIP, "dv_voice_capture: hipMalloc of a %zu-byte record failed", bytes); }
+    v->bytes = bytes; v->sig = u->cond_sig;
+    recs.push_back(v->rec);
+  }
+  // set_cond ran on a stream this call does not know: wait for the device, snapshot, wait again - the records are complete on return
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = launch_voice_gather(u->cond_segs_dev, (int)u->cond_segs.size(), u->cond_chunks, rows, recs.data(), n, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { drop(); return dv_fail(DV_ERR_HIP, "dv_voice_capture: %s", hipGetErrorString(e)); }
+  for (int i = 0; i < n; ++i) out[i] = vs[i];
+  return DV_OK;
+}
+
+extern "C" int dv_unet_bind_voices(dv_unet* u, const int32_t* rows, dv_voice* const* voices, int32_t n, void* stream) {
+  if (!u || !rows || !voices || n < 1) return dv_fail(DV_ERR_INVALID, "dv_unet_bind_voices: bad argument");
+  if (!u->prepared || !u->cond_chunks) return dv_fail(DV_ERR_STATE, "dv_unet_bind_voices before dv_unet_prepare");
+  if (int rc = voice_rows_ok(u, rows, n, true, "dv_unet_bind_voices")) return rc;
+  std::vector<void*> recs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const dv_voice* v = voices[i];
+    if (!v || !v->rec) return dv_fail(DV_ERR_INVALID, "dv_unet_bind_voices: entry %d is not a voice", i);
+    if (v->sig != u->cond_sig || v->bytes != (size_t)u->cond_chunks * 16)
+      return dv_fail(DV_ERR_INVALID, "dv_unet_bind_voices: the voice for row %d was recorded under layout %016llx, this schedule has %016llx",
+                     rows[i], (unsigned long long)v->sig, (unsigned long long)u->cond_sig);
+    recs[i] = v->rec;
+  }
+  HIPCHK(launch_voice_scatter(u->cond_segs_dev, (int)u->cond_segs.size(), u->cond_chunks, rows, recs.data(), n, (hipStream_t)stream));
+  for (int i = 0; i < n; ++i) u->row_cond[rows[i]] = 1;
+  bool all = true;
+  for (uint8_t f : u->row_cond) all = all && f;
+  if (all) u->cond_set = true;
+  return DV_OK;
 }
 
 // In-kernel hand-over health (GnxParams): *n_ops = GEMMs of the schedule that finish their consumer's GroupNorm in the

@@ -127,18 +127,20 @@ template <int BK> struct Tiles {
     if ((e = T4::init()) != hipSuccess) return e;
     return T4G::init();
   }
-  static hipError_t launch(const GemmParams& p, bool x3, int min_wg, bool ksplit, hipStream_t st) {
-    auto cnt = [&](int bm, int bn) { return ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
-    if (p.epi == EPI_GEGLU) {
-      if (cnt(128, 64) >= min_wg) return T1::launch(p, x3, st);
-      if (cnt(64, 64) >= min_wg) return T2G::launch(p, x3, st);
-      return T4G::launch(p, x3, st);
+  // the instantiation gemm_variant (below: the ONE place where the shape heuristic lives) chose, by its id BM | BN << 8 | BK << 16 |
+  // k-groups << 24
+  static hipError_t launch_variant(const GemmParams& p, bool x3, int v, hipStream_t st) {
+    const int bm = v & 255, bn = (v >> 8) & 255, kg = v >> 24;
+    if (bm == 128 && bn == 128) return kg == 2 ? T0::launch(p, x3, st) : T0S::launch(p, x3, st);
+    if (bm == 128 && bn == 64) return T1::launch(p, x3, st);
+    if (bm == 64 && bn == 64) {
+      if (p.epi == EPI_GEGLU) return T2G::launch(p, x3, st);
+      return (BK == 64 && kg == 2) ? T2::launch(p, x3, st) : T2S::launch(p, x3, st);
     }
-    static const int t1_min = [] { const char* e = getenv("DVITS_GEMM_T1"); return e ? atoi(e) : 192; }();   // 128x64 tiles from 192 of them: 384+ 64x64 tiles would run as two rounds, and would not fit the in-launch GroupNorm hand-over (round 4: 256 -> 192, +0.4 % same box)
-    if (BK == 64 && cnt(128, 64) >= t1_min) return T1::launch(p, x3, st);
-    if (cnt(64, 64) >= min_wg) return ksplit ? T2::launch(p, x3, st) : T2S::launch(p, x3, st);
-    if (cnt(64, 32) >= min_wg) return T3::launch(p, x3, st);
-    return T4::launch(p, x3, st);
+    if (bm == 64 && bn == 32) return T3::launch(p, x3, st);
+    if (bm == 32 && bn == 32) return T4::launch(p, x3, st);
+    if (bm == 32 && bn == 64) return T4G::launch(p, x3, st);
+    return hipErrorInvalidValue;
   }
   static hipError_t launch_forced(const GemmParams& p, bool x3, int tile, hipStream_t st) {
     switch (tile) {
@@ -225,25 +227,55 @@ void gemm_env_refresh() {
   conv3_env_refresh();
 }
 
-// Tile (BM x BN) the shape heuristic of launch_gemm picks for a non-GEGLU GEMM (kept in step with
-// Tiles<BK>::launch below; used to plan the in-epilogue GroupNorm: its tiles must not span utterances and must all be resident)
+// Tile (BM x BN) the shape heuristic picks (gemm_variant below, whatever force_tile says); used to plan the in-epilogue
+// GroupNorm: its tiles must not span utterances and must all be resident
+int gemm_variant(const GemmParams& p);
 static void gemm_pick_tile(const GemmParams& p, int& bm, int& bn) {
+  GemmParams q = p;
+  q.force_tile = GT_AUTO;
+  const int v = gemm_variant(q);
+  bm = v & 255; bn = (v >> 8) & 255;
+}
+
+// Which k_gemm instantiation a GEMM runs on, as BM | BN << 8 | BK << 16 | k-groups << 24: the shape heuristic of launch_gemm (it
+// dispatches on this function's result: Tiles<BK>::launch_variant) and the table of the forced tiles.  The tile decides how a
+// row's dot products are cut into partial sums (BK, the k-groups of a workgroup), i.e. the float32 rounding of the result: a
+// caller that keeps results across schedules (the voice records of engine.hip) keys them on it.
+int gemm_variant(const GemmParams& p) {
   const GemmTune& tune = gemm_tune();
+  auto id = [](int bm, int bn, int bk, int kg) { return bm | bn << 8 | bk << 16 | kg << 24; };
   auto cnt = [&](int a, int b) { return ((p.M + a - 1) / a) * ((p.N + b - 1) / b); };
   bool k64 = tune.bk64 != 0;
   for (int s = 0; s < p.nseg; ++s) k64 = k64 && p.seg[s].c0 % 64 == 0 && p.seg[s].c1 % 64 == 0;
-  if (cnt(128, 128) >= tune.big) { bm = 128; bn = 128; return; }
-  const int min_wg = k64 ? tune.min_wg : (tune.min_wg > 0 ? tune.min_wg : 1);
-  if (p.epi == EPI_GEGLU) {
-    if (cnt(128, 64) >= min_wg) { bm = 128; bn = 64; return; }
-    if (cnt(64, 64) >= min_wg) { bm = 64; bn = 64; return; }
-    bm = 32; bn = 64; return;
+  const int ft = p.force_tile & 0xff;
+  if (ft != GT_AUTO) {
+    const int bk = (p.force_tile & GT_BK64) ? 64 : 32, kg2 = bk == 64 ? 2 : 1;
+    switch (ft) {
+      case GT_T0: return id(128, 128, 32, 2);
+      case GT_T1: return id(128, 64, bk, kg2);
+      case GT_T2: return id(64, 64, bk, kg2);
+      case GT_T2S: return id(64, 64, bk, 1);
+      case GT_T2G: return id(64, 64, bk, 1);
+      case GT_T3: return id(64, 32, bk, kg2);
+      case GT_T4: return id(32, 32, bk, kg2);
+      case GT_T4G: return id(32, 64, bk, 1);
+      default: return -1;
+    }
   }
-  static const int t1_min = [] { const char* e = getenv("DVITS_GEMM_T1"); return e ? atoi(e) : 192; }();
-  if (k64 && cnt(128, 64) >= t1_min) { bm = 128; bn = 64; return; }
-  if (cnt(64, 64) >= min_wg) { bm = 64; bn = 64; return; }
-  if (cnt(64, 32) >= min_wg) { bm = 64; bn = 32; return; }
-  bm = 32; bn = 32;
+  if (cnt(128, 128) >= tune.big) return id(128, 128, 32, tune.ksplit ? 2 : 1);
+  const int bk = k64 ? 64 : 32, kg2 = bk == 64 ? 2 : 1;
+  const int min_wg = bk == 64 ? tune.min_wg : (tune.min_wg > 0 ? tune.min_wg : 1);
+  const bool ksplit = bk == 64 && tune.ksplit != 0;
+  if (p.epi == EPI_GEGLU) {
+    if (cnt(128, 64) >= min_wg) return id(128, 64, bk, kg2);
+    if (cnt(64, 64) >= min_wg) return id(64, 64, bk, 1);
+    return id(32, 64, bk, 1);
+  }
+  static const int t1_min = [] { const char* e = getenv("DVITS_GEMM_T1"); return e ? atoi(e) : 192; }();   // 128x64 tiles from 192 of them: 384+ 64x64 tiles would run as two rounds, and would not fit the in-launch GroupNorm hand-over (round 4: 256 -> 192, +0.4 % same box)
+  if (bk == 64 && cnt(128, 64) >= t1_min) return id(128, 64, bk, kg2);
+  if (cnt(64, 64) >= min_wg) return ksplit ? id(64, 64, bk, kg2) : id(64, 64, bk, 1);
+  if (cnt(64, 32) >= min_wg) return id(64, 32, bk, kg2);
+  return id(32, 32, bk, kg2);
 }
 
 // XCD rectangle of a tm x tn tile grid run as xs k-slices (fills p.xcd_*; xcd_n = 0: row bands of the tile grid)
@@ -397,20 +429,17 @@ hipError_t launch_gemm(const GemmParams& pin, int precision, hipStream_t st) {
   // (the caller - engine.hip conv3_takes - gives the fragment-major weights only where this kernel is the better one)
   if (c3) return launch_conv3(p, st);
   if (p.c3_route == 2 && p.sk_mode == 0) return launch_conv3_up(p, st);
-  const GemmTune& tune = gemm_tune();
-  const int big_tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
-  bool k64 = tune.bk64 != 0;
+  bool k64 = gemm_tune().bk64 != 0;
   for (int s = 0; s < p.nseg; ++s) k64 = k64 && p.seg[s].c0 % 64 == 0 && p.seg[s].c1 % 64 == 0;
   const int ft = p.force_tile & 0xff;
   if (ft != GT_AUTO && (p.force_tile & GT_BK64) && !k64) return hipErrorInvalidValue;
-  const bool big = ft != GT_AUTO ? ft == GT_T0 : big_tiles >= tune.big;
-  const int bk = ft != GT_AUTO ? ((p.force_tile & GT_BK64) ? 64 : 32) : ((!big && k64) ? 64 : 32);
+  const int variant = gemm_variant(p);
+  if (variant < 0) return hipErrorInvalidValue;
+  const int bk = ft != GT_AUTO ? ((p.force_tile & GT_BK64) ? 64 : 32) : (variant >> 16) & 255;
   for (int s = 0; s < p.nseg; ++s) {
     if (p.seg[s].c0 % 32 != 0 || p.seg[s].c1 % 32 != 0) return hipErrorInvalidValue;
     p.seg[s].nkt = p.seg[s].taps * (p.seg[s].c0 + p.seg[s].c1) / bk;
   }
   if (ft != GT_AUTO) return bk == 64 ? Tiles<64>::launch_forced(p, x3, ft, st) : Tiles<32>::launch_forced(p, x3, ft, st);
-  if (big) return tune.ksplit ? Tiles<32>::T0::launch(p, x3, st) : Tiles<32>::T0S::launch(p, x3, st);
-  if (bk == 64) return Tiles<64>::launch(p, x3, tune.min_wg, tune.ksplit != 0, st);
-  return Tiles<32>::launch(p, x3, tune.min_wg > 0 ? tune.min_wg : 1, false, st);
+  return bk == 64 ? Tiles<64>::launch_variant(p, x3, variant, st) : Tiles<32>::launch_variant(p, x3, variant, st);
 }

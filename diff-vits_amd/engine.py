@@ -60,6 +60,49 @@ def _verify_at_exit():
 atexit.register(_verify_at_exit)
 
 
+class Voice:
+    """An enrolled speaker prompt: the conditioning `UNetEngine.set_cond` derives from it, kept so that it can be bound to any
+    batch row later (`UNetEngine.enroll` / `bind_voices`, `NaturalSpeech2.enroll_voice`).
+
+    On the HIP engine it owns a native record (dv_voice_*: the row's slice of every persistent conditioning buffer, device
+    memory of its own) with the layout `signature` it was taken under, the weight identity of the denoiser at that time
+    (`weight_sig`, what `sync_weights` compares) and the prompt's encoder states themselves - `enc` [1, L, D], `bias` [1, L] or
+    None - from which a record is derived again when a schedule has another signature: it keeps the conditioning in another
+    form, or runs the K / V projections on another GEMM tile, which rounds them differently (`rebuilds` counts that).  The voice
+    keeps one record per signature it has met (`nbytes` is their sum), so batches of alternating sizes derive each once.
+    A voice of the torch backend holds `enc` and `mask` only.  `refer` [1, 100, L] / `refer_length` [1], where enrolment knew
+    them, are the mel prompt for the prior (`tts_infer.synthesize`)."""
+
+    def __init__(self, enc, bias=None, mask=None, handle=None, signature=0, weight_sig=None):
+        self.enc, self.bias, self.mask = enc, bias, mask
+        self.L = int(enc.shape[1])
+        self._h = handle                      # the record made last, under `signature`
+        self._recs = {signature: handle} if handle else {}
+        self.signature, self.weight_sig = signature, weight_sig
+        self.rebuilds = 0
+        self.refer = self.refer_length = None
+
+    @property
+    def nbytes(self):
+        """Device bytes of the native records (0: a torch-backend voice)."""
+        return sum(int(_lib.lib().dv_voice_bytes(h)) for h in self._recs.values())
+
+    def _add(self, handle, signature):
+        self._recs[signature] = handle
+        self._h, self.signature = handle, signature
+
+    def _drop(self):
+        for h in getattr(self, "_recs", {}).values():
+            sys.modules["diff_vits_amd._lib"].lib().dv_voice_destroy(h)
+        self._recs, self._h = {}, None
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
+
+
 class UNetEngine:
     def __init__(self, module):
         self.module = module
@@ -205,8 +248,7 @@ class UNetEngine:
             raise ValueError("precision must be one of %s" % sorted(_PRECISIONS))
         # cheap change detector first (no state_dict() with its 701 prefixed names per call): storage address + version
         # counter of every parameter / buffer; load_state_dict, .to() and in-place updates all move one of them
-        m = self.module
-        sig = tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
+        sig = self._module_sig()
         if sig != self._sig:             # new parameters: every cached schedule is stale
             self._sig = sig
             self._prepared = None
@@ -214,6 +256,10 @@ class UNetEngine:
             self.precision = precision
             self._prepared = None
         self._upload(self._cur)
+
+    def _module_sig(self):
+        m = self.module
+        return tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
 
     def _upload(self, slot):
         """Give `slot`'s native handle the module's current parameters if it does not have them yet."""
@@ -279,6 +325,130 @@ class UNetEngine:
         self.cond_serial += 1
         self.check_or_recover(_lib.lib().dv_unet_set_cond(self._h, _lib.ptr(enc), _lib.ptr(bias), _lib.stream_ptr()),
                               "dv_unet_set_cond")
+
+    # ------------------------------------------------------------------ enrolled voices
+    def cond_signature(self):
+        """Layout signature of the current schedule's conditioning (dv_unet_cond_signature; 0 before prepare)."""
+        return int(_lib.lib().dv_unet_cond_signature(self._h))
+
+    def _cond_rows(self, flags=None):
+        """The native handle's own record of which batch rows are conditioned (dv_unet_cond_rows): read, or overwritten."""
+        B = self._cur.prepared[0]
+        arr = (C.c_uint8 * B)(*([0] * B if flags is None else [1 if f else 0 for f in flags]))
+        _lib.check(_lib.lib().dv_unet_cond_rows(self._h, arr, B, 0 if flags is None else 1), "dv_unet_cond_rows")
+        return [bool(f) for f in arr]
+
+    def _capture(self, rows):
+        """Native records of batch rows of the current conditioning -> list of (handle, signature)."""
+        n = len(rows)
+        arr = (C.c_int32 * n)(*rows)
+        out = (C.c_void_p * n)()
+        _lib.check(_lib.lib().dv_voice_capture(self._h, arr, n, out), "dv_voice_capture")
+        return [(C.c_void_p(h), int(_lib.lib().dv_voice_signature(C.c_void_p(h)))) for h in out]
+
+    def _cond_chunks(self, encs, biases):
+        """set_cond on chunks of B prompts (a short last chunk is filled by repeating its last prompt); yields the number of
+        real rows of each chunk once it is conditioned."""
+        B = self._cur.prepared[0]
+        for i in range(0, len(encs), B):
+            idx = list(range(i, min(i + B, len(encs))))
+            pad = idx + [idx[-1]] * (B - len(idx))
+            enc = torch.cat([encs[j] for j in pad])
+            bias = None if biases[idx[0]] is None else torch.cat([biases[j] for j in pad])
+            self.set_cond(enc, bias)
+            yield len(idx)
+
+    def enroll(self, enc, bias=None):
+        """enc [n, L, D], bias additive [n, L] / [n, 1, L] or None (GPU tensors) -> n `Voice`s: what `set_cond` derives from
+        each prompt, snapshotted.  Runs on the currently prepared schedule (prepare first; L must be its L) in chunks of its
+        B rows and, like any `set_cond`, overwrites the engine's current conditioning and bumps `cond_serial`."""
+        if self._cur.prepared is None or self._module_sig() != self._sig:
+            raise RuntimeError("enroll needs a prepared schedule with the module's current weights: sync_weights() and prepare(B, T, L) first")
+        if not enc.is_cuda or (bias is not None and not bias.is_cuda):
+            raise ValueError("enroll needs GPU tensors; got enc on %s" % enc.device)
+        n, L, D = enc.shape
+        if L != self._cur.prepared[2] or D != self.cross_dim:
+            raise ValueError("enroll: enc must be [n, L=%d, %d] for the prepared schedule, got %s" % (self._cur.prepared[2], self.cross_dim, tuple(enc.shape)))
+        enc = enc.detach().to(torch.float32).contiguous()
+        encs = [enc[i:i + 1].clone() for i in range(n)]
+        biases = [None] * n
+        if bias is not None:
+            bias = bias.detach().to(torch.float32).reshape(n, L)
+            biases = [bias[i:i + 1].clone() for i in range(n)]
+        voices, i = [], 0
+        for m in self._cond_chunks(encs, biases):
+            for h, sig in self._capture(list(range(m))):
+                voices.append(Voice(encs[i], biases[i], handle=h, signature=sig, weight_sig=self._sig))
+                i += 1
+        return voices
+
+    def bind_voices(self, rows, voices):
+        """Write `voices[i]` into batch row `rows[i]` of the current schedule's conditioning - one scatter launch on the current
+        stream, capturable while no voice has to be rebuilt (below: a rebuild waits for the device) - in place of the `set_cond`
+        that would have computed the same bytes.  Rows not named keep what they
+        have; a forward needs every row conditioned since the schedule was planned, by `set_cond` or by binds.
+
+        Refused before anything is launched: a voice without a native record or on the CPU, or made under other weights than
+        the engine holds - as of its last `sync_weights`, which must have run since the module last changed (`unet.hip_engine()`
+        runs it; a module mutated in place and bound without it is not noticed here, as `set_cond` would not notice it either) -
+        or with another key length L than the schedule's (ValueError / RuntimeError naming the row), a row outside the batch, a row
+        named twice.  A voice without a record of this schedule's signature (a schedule that keeps K / V in another form, or
+        whose batch puts the K / V projections on another GEMM tile) is not an error: one is derived from the stored encoder
+        states by one conditioning pass
+        (`voice.rebuilds` += 1; the pass uses the schedule's own rows: the conditioned rows that are not being bound are saved
+        and restored around it, and rows that were unconditioned before are unconditioned after), then bound.
+        Bumps `cond_serial`."""
+        rows = [int(r) for r in rows]
+        voices = list(voices)
+        if len(rows) != len(voices) or not rows:
+            raise ValueError("bind_voices needs as many rows as voices, at least one; got %d rows, %d voices" % (len(rows), len(voices)))
+        if self._cur.prepared is None:
+            raise RuntimeError("bind_voices before prepare")
+        B, _, L = self._cur.prepared[:3]
+        # (the weights as of the last sync_weights - what the schedule was packed from; `unet.hip_engine()` syncs.  The identity
+        # test keeps the common case off the 1400-entry comparison: a bind must stay cheaper than the pass it replaces)
+        cur_sig = self._sig
+        for r, v in zip(rows, voices):
+            if not isinstance(v, Voice):
+                raise ValueError("row %d: expected a Voice, got %s" % (r, type(v).__name__))
+            if not v._recs or not v.enc.is_cuda:
+                raise ValueError("row %d: the voice holds CPU tensors / no native record (enrolled on the torch backend); "
+                                 "enrol it on the GPU engine" % r)
+            if v.weight_sig is not cur_sig and v.weight_sig != cur_sig:
+                raise RuntimeError("row %d: the denoiser's weights changed since this voice was enrolled; enrol it again" % r)
+            if v.L != L:
+                raise ValueError("row %d: the voice has key length L = %d, the schedule L = %d" % (r, v.L, L))
+            if not 0 <= r < B:
+                raise ValueError("row %d is outside the schedule's batch of %d" % (r, B))
+        if len(set(rows)) != len(rows):
+            raise ValueError("bind_voices: a row is named twice: %s" % (rows,))
+        sig = self.cond_signature()
+        stale = list({id(v): v for v in voices if sig not in v._recs}.values())
+        if stale:
+            was = self._cond_rows()
+            keep = [r for r in range(B) if was[r] and r not in rows]
+            saved = self._capture(keep) if keep else []
+            i = 0
+            for m in self._cond_chunks([v.enc for v in stale], [v.bias for v in stale]):
+                for h, s in self._capture(list(range(m))):
+                    stale[i]._add(h, s)
+                    stale[i].rebuilds += 1
+                    i += 1
+            if saved:
+                self._bind_native(keep, [h for h, _ in saved])
+                torch.cuda.current_stream().synchronize()
+                for h, _ in saved:
+                    _lib.lib().dv_voice_destroy(h)
+            self._cond_rows([r in keep for r in range(B)])     # (the pass marked every row: hand the truth back)
+        self._bind_native(rows, [v._recs[sig] for v in voices])
+        self._cur.cond_keepalive = tuple(voices)      # (the launch reads the records: they live at least until the next conditioning)
+        self.cond_serial += 1
+        self._fwd_cond = None
+
+    def _bind_native(self, rows, handles):
+        n = len(rows)
+        _lib.check(_lib.lib().dv_unet_bind_voices(self._h, (C.c_int32 * n)(*rows), (C.c_void_p * n)(*[h.value for h in handles]), n,
+                                                  _lib.stream_ptr()), "dv_unet_bind_voices")
 
     def check_or_recover(self, rc, what):
         """`_lib.check` for the calls that start with the native health check (set_cond, forward, dv_sampler_run): if the

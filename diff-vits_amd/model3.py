@@ -332,19 +332,66 @@ class NaturalSpeech2(nn.Module):
         nenc = self.diff_model.prompt_encoder.encode_channels_last(negative_refer, negative_lengths) * nmask.unsqueeze(-1).to(enc.dtype)
         return enc, mask, F.pad(nenc.to(enc), (0, 0, 0, L - Ln)), F.pad(nmask.to(torch.bool), (0, L - Ln))
 
+    def _prompt_sig(self):
+        return tuple((p.data_ptr(), p._version) for p in self.diff_model.prompt_encoder.parameters())
+
     @torch.no_grad()
-    def sample_from_prior(self, content, refer, text_lengths, spec_lengths, vocos=None, sample_method="unipc", noise=None,
-                          guidance_scale=1.0, negative_refer=None, negative_lengths=None):
+    def enroll_voice(self, refer, spec_lengths, T=None):
+        """Speaker prompts refer [n, 100, L] with their frame counts spec_lengths [n] -> n `engine.Voice`s for
+        `sample_from_prior(voices=)`: the prompt encoder runs once, here, and on the HIP backend the denoiser's conditioning
+        (pooled-text embedding, the cross-attention K / V of the 16 blocks, the key bias) is computed once and kept as a
+        native record per voice.  The engine is prepared at (B = n, T (default 32), L) for that - any later schedule with the
+        same L binds the voices.  On the torch backend a voice holds the encoder states and the mask."""
+        from .engine import Voice
+        dm = self.diff_model
+        n, L = refer.shape[0], refer.shape[2]
+        mask = sequence_mask(spec_lengths, L)
+        enc = dm.prompt_encoder.encode_channels_last(refer, spec_lengths) * mask.unsqueeze(-1).to(torch.float32)
+        mask = mask.to(torch.bool)
+        if dm.backend == "hip" and refer.is_cuda:
+            eng = dm.unet.hip_engine()          # (hands the module's current weights over)
+            eng.prepare(n, 32 if T is None else int(T), L)
+            voices = eng.enroll(enc, dm.unet._bias_from_mask(mask, torch.float32))
+        else:
+            voices = [Voice(enc[i:i + 1].clone()) for i in range(n)]
+        psig = self._prompt_sig()
+        for i, v in enumerate(voices):
+            v.prompt_sig = psig          # (Voice.weight_sig knows the denoiser only: the states came out of THIS prompt encoder)
+            v.mask = mask[i:i + 1].clone()
+            v.refer, v.refer_length = refer[i:i + 1].clone(), spec_lengths[i:i + 1].clone()
+        return voices
+
+    @torch.no_grad()
+    def sample_from_prior(self, content, refer=None, text_lengths=None, spec_lengths=None, vocos=None, sample_method="unipc", noise=None,
+                          guidance_scale=1.0, negative_refer=None, negative_lengths=None, voices=None):
         """(content, refer) -> (audio | None, mel): reference model3.py:1162-1203 after the `vits.infer` call.
         guidance_scale != 1: classifier-free guidance (model_wrapper(guidance_type='classifier-free'), dpm_solver.py:322-330)
         between the speaker prompt and `negative_refer` [B, 100, L'] with `negative_lengths` (None: all-zero encoder states
         under the prompt's mask) - on the HIP backend inside the one hipGraph, on the torch backend through the mirror's
-        generic path.  With the defaults nothing changes."""
+        generic path.  With the defaults nothing changes.
+        voices: one enrolled `Voice` per batch row (`enroll_voice`) in place of `refer` / `spec_lengths`, which may then be
+        None: the prompt encoder and the denoiser's conditioning pass are skipped - the HIP engine binds the voices' records to
+        the rows (`UNetEngine.bind_voices`), the torch backend takes their encoder states.  Not together with guidance."""
         if sample_method not in ("unipc", "dpmsolver"):
             raise ValueError("sample_method %r is not supported (this build: 'unipc', 'dpmsolver')" % (sample_method,))
         guided = float(guidance_scale) != 1.0
         shape = (content.shape[0], self.dim, content.shape[2])
-        audio = torch.randn(shape, device=refer.device) if noise is None else noise.to(refer.device)
+        if voices is not None:
+            voices = list(voices)
+            if guided:
+                raise ValueError("voices= cannot be combined with guidance_scale != 1 (binding the 2B rows of a guided run is not supported)")
+            if len(voices) != content.shape[0]:
+                raise ValueError("voices must hold one Voice per batch row: %d rows, %d voices" % (content.shape[0], len(voices)))
+            psig = self._prompt_sig()
+            for i, v in enumerate(voices):
+                if getattr(v, "prompt_sig", psig) != psig:
+                    raise RuntimeError("row %d: the prompt encoder's weights changed since this voice was enrolled; enrol it again" % i)
+            if len({v.L for v in voices}) != 1:
+                raise ValueError("the voices of one batch must share their key length L, got %s" % sorted({v.L for v in voices}))
+        elif refer is None:
+            raise ValueError("sample_from_prior needs `refer` (with `spec_lengths`) or `voices`")
+        dev = content.device if refer is None else refer.device
+        audio = torch.randn(shape, device=dev) if noise is None else noise.to(dev)
         if tuple(audio.shape) != shape:
             raise ValueError("noise must have shape %s, got %s" % (shape, tuple(audio.shape)))
         data = (content, refer, text_lengths, spec_lengths)
@@ -380,15 +427,31 @@ class NaturalSpeech2(nn.Module):
             ent = cache.get(sample_method)
             if ent is None or ent["betas"] != bkey:
                 noise_schedule = NoiseScheduleVP(schedule="discrete", betas=self.betas)
-                nm = self.diff_model.native_model(data)
+                if voices is not None:
+                    from .sampler._plan import NativeUNetModel
+                    nm = NativeUNetModel(self.diff_model.unet, content, None, None)
+                else:
+                    nm = self.diff_model.native_model(data)
                 model_fn = model_wrapper(nm, noise_schedule, model_type="x_start")
                 solver = (UniPC(model_fn, noise_schedule, variant="bh2") if sample_method == "unipc"
                           else DPM_Solver(model_fn, noise_schedule, algorithm_type="dpmsolver++"))
                 ent = cache[sample_method] = {"betas": bkey, "native": nm, "solver": solver}
-            else:
+            elif voices is None:
                 enc, mask = self.diff_model._conditioning(refer, spec_lengths, torch.float32)
                 ent["native"].cond, ent["native"].enc, ent["native"].mask = content, enc, mask
+            else:
+                ent["native"].cond = content
+            ent["native"].voices = voices            # (None: set_cond on enc / mask as ever; a list: bound row by row)
             solver = ent["solver"]
+        elif voices is not None:
+            # the mirror's forward (Diffusion_Encoder.forward, torch branch) on the voices' stored encoder states
+            noise_schedule = NoiseScheduleVP(schedule="discrete", betas=self.betas)
+            venc, vmask = torch.cat([v.enc for v in voices]).to(dev), torch.cat([v.mask for v in voices]).to(dev)
+            unet = self.diff_model.unet
+            model_fn = model_wrapper(lambda x, t: unet(torch.cat([x, content], dim=1), t, venc, encoder_attention_mask=vmask).sample,
+                                     noise_schedule, model_type="x_start")
+            solver = (UniPC(model_fn, noise_schedule, variant="bh2") if sample_method == "unipc"
+                      else DPM_Solver(model_fn, noise_schedule, algorithm_type="dpmsolver++"))
         else:
             noise_schedule = NoiseScheduleVP(schedule="discrete", betas=self.betas)
             model_fn = model_wrapper(self.sample_fun, noise_schedule, model_type="x_start", model_kwargs={"data": data})
@@ -425,10 +488,12 @@ class NaturalSpeech2(nn.Module):
 
     @torch.no_grad()
     def sample(self, text, spec, text_lengths, spec_lengths, tone, language, vocos, sampling_timesteps=200,
-               sample_method="unipc", noise=None, prior_noise=None, guidance_scale=1.0, negative_refer=None, negative_lengths=None):
+               sample_method="unipc", noise=None, prior_noise=None, guidance_scale=1.0, negative_refer=None, negative_lengths=None,
+               voices=None):
         """reference model3.py:1119-1203 (same positional signature).  `noise` = x_T, `prior_noise` = the prior's
         normal draw (forwarded as `noise=` to this package's VITS.infer); both default to fresh torch.randn draws.
-        guidance_scale / negative_refer / negative_lengths: classifier-free guidance, see sample_from_prior."""
+        guidance_scale / negative_refer / negative_lengths: classifier-free guidance, see sample_from_prior.
+        voices: enrolled voices for the diffusion side (sample_from_prior); the prior still reads `spec` / `spec_lengths`."""
         self.sampling_timesteps = sampling_timesteps
         if not hasattr(self, "vits"):
             raise RuntimeError("NaturalSpeech2.sample needs the VITS prior: construct with vits=<module with .infer(...)> "
@@ -438,7 +503,7 @@ class NaturalSpeech2(nn.Module):
         else:
             content, refer = self.vits.infer(text, text_lengths, spec, spec_lengths, tone, language, noise=prior_noise)
         return self.sample_from_prior(content, refer, text_lengths, spec_lengths, vocos, sample_method, noise,
-                                      guidance_scale, negative_refer, negative_lengths)
+                                      guidance_scale, negative_refer, negative_lengths, voices=voices)
 
 
 # ---- SURVEY.md §8f rank 3 (inference side of the VITS prior, from the text encoder's outputs onward) ------------------

@@ -388,6 +388,8 @@ class NativeUNetModel:
     solver path keeps working.  Holds this package's UNet (backend='hip'), the channel-concat
     condition `cond` [B, in-out, T] and the cross-attention inputs."""
 
+    voices = None       # a list of engine.Voice, one per batch row: run_plan binds them instead of set_cond on enc / mask
+
     def __init__(self, unet, cond, encoder_hidden_states, encoder_attention_mask=None, uncond_mask=None):
         self.unet, self.cond, self.enc, self.mask = unet, cond, encoder_hidden_states, encoder_attention_mask
         self.uncond_mask = uncond_mask      # key mask of the unconditional half of a guided evaluation (None: `mask`)
@@ -404,6 +406,9 @@ class NativeUNetModel:
         """`cond` (the reference's third positional argument, dpm_solver.py:284-287): encoder hidden states [n, L, D] in place
         of the stored ones; n = twice the stored batch is a guided evaluation [unconditional | conditional]: the
         channel-concat condition and the masks are repeated."""
+        if self.voices is not None:
+            # (enc / mask are None or a previous utterance's here: conditioning on them would speak with the wrong voice)
+            raise RuntimeError("enrolled voices run as one native graph only (no intermediates, no correction hooks, no call by call)")
         if cond is None:
             sample = x if self.cond is None else torch.cat([x, self.cond], dim=1)
             return self.unet(sample, t_input, self.enc, encoder_attention_mask=self.mask).sample
@@ -438,6 +443,14 @@ class NativeUNetModel:
     def _run_plan_once(self, plan, x, eng, L, guidance=None):
         B, C_, T = x.shape
         eng.before_enqueue()             # (lazy verification: a run before a long host pause is verified here - engine.py)
+        if self.voices is not None:
+            if guidance is not None:
+                raise ValueError("enrolled voices cannot be combined with classifier-free guidance")
+            if len(self.voices) != B:
+                raise RuntimeError("%d voices do not match x batch %d" % (len(self.voices), B))
+            eng.prepare(B, T, self.voices[0].L)
+            eng.bind_voices(range(B), self.voices)
+            return self._replay(plan, x, eng, L)
         enc, mask, scale = self.enc, self.mask, None
         if guidance is not None:
             enc = guidance["condition"]
@@ -455,6 +468,9 @@ class NativeUNetModel:
         eng.set_cond(enc, bias)
         if scale is not None:
             plan = plan.with_guidance(scale)
+        return self._replay(plan, x, eng, L)
+
+    def _replay(self, plan, x, eng, L):
         # Persistent input / condition buffers per shape: the captured graph is keyed on their addresses (and on the
         # engine's schedule handle), so a new utterance of a shape seen before replays its graph instead of re-capturing
         # steps x ~160 launches.  (Bounded: the engine keeps DVITS_PLAN_CACHE schedules.)

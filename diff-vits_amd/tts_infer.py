@@ -13,6 +13,7 @@ part of the inference model and are skipped when loading; every key the inferenc
 """
 import torch
 
+from .engine import Voice
 from .mel import reference_mel_prompt
 from .model3 import VITS, NaturalSpeech2
 
@@ -88,16 +89,27 @@ def synthesize(model, cfg, vocos, batchs, control_values=None, device="cuda", pr
 
     prompt_length: tts_infer.py:68 passes `refer.size(1)` - the mel CHANNEL count, 100 - as the prompt length, so the
     prompt masks cover the first 100 frames whatever the audio's length.  "reference" keeps that; "frames" passes the
-    real frame count `refer.size(2)`."""
+    real frame count `refer.size(2)`.
+
+    A batch tuple's `refer` may also be an enrolled `Voice` (`model.enroll_voice`): the diffusion side then binds the voice
+    instead of encoding the prompt again; the prior still reads the mel prompt and the length the voice was enrolled with
+    (`voice.refer`, `voice.refer_length`)."""
     if prompt_length not in ("reference", "frames"):
         raise ValueError("prompt_length must be 'reference' or 'frames'")
     samples = mel = None
     for phoneme, tone, language, refer, phoneme_length in batchs:
         phoneme, tone, language = phoneme.to(device), tone.to(device), language.to(device)
         phoneme_length = torch.as_tensor(phoneme_length, dtype=torch.long).to(device)
-        spec = refer_prompt(refer, device)
-        refer_length = torch.tensor([spec.size(1) if prompt_length == "reference" else spec.size(2)]).to(device)
+        if isinstance(refer, Voice):
+            if refer.refer is None:
+                raise ValueError("a Voice in a batch tuple must carry its mel prompt (enrol it with model.enroll_voice): the prior reads it")
+            spec, refer_length = refer.refer.to(device), refer.refer_length.to(device)
+            kw = dict(sample_kw, voices=[refer])
+        else:
+            spec = refer_prompt(refer, device)
+            refer_length = torch.tensor([spec.size(1) if prompt_length == "reference" else spec.size(2)]).to(device)
+            kw = sample_kw
         with torch.no_grad():
-            samples, mel = model.sample(phoneme, spec, phoneme_length, refer_length, tone, language, vocos, **sample_kw)
+            samples, mel = model.sample(phoneme, spec, phoneme_length, refer_length, tone, language, vocos, **kw)
         samples = samples.detach().cpu()
     return samples, mel

@@ -91,6 +91,7 @@ typedef struct dv_unet dv_unet;
 typedef struct dv_plan dv_plan;
 typedef struct dv_penc dv_penc;
 typedef struct dv_tenc dv_tenc;
+typedef struct dv_voice dv_voice;
 
 const char* dv_last_error(void);
 /* Library/version probe: returns e.g. "dvits_hip 0.1 gfx950". */
@@ -190,6 +191,44 @@ int dv_unet_persist_ticks(dv_unet* u, int32_t* first_op, uint64_t* ticks, int32_
  * "conv_in", "emb", "down_blocks.0.resnets.0", "down_blocks.0.attentions.0",
  * "mid_block.resnets.1", "up_blocks.1.upsamplers.0". */
 int dv_unet_probe(dv_unet* u, const char* name, float* host_out, int64_t capacity, int64_t* dims);
+
+/* ---- enrolled voices: the conditioning of one speaker prompt, kept and bound to batch rows --------------------------------
+ * Everything dv_unet_set_cond computes depends on the prompt alone.  At prepare time the engine records which persistent
+ * buffers the conditioning schedule writes and the step schedule reads (the K / V^T fragments of the 16 transformer blocks,
+ * the key-bias rows, the pooled-text row; the fp32 K | V and the mask bias where a block's attention still reads them) - the
+ * conditioning segment table, every buffer utterance-major.  A voice record is one row of all of them, laid end to end in
+ * 16-byte chunks (a segment whose bytes per utterance are no multiple of 16 is padded in the record, never in the buffer).
+ * No arithmetic: binding a record writes, byte for byte, what dv_unet_set_cond wrote into the row it was taken from.
+ *
+ * Layout signature: a hash over the engine configuration, the precision, L and every segment's kind and size - not over B
+ * or T.  A record binds to any schedule with its signature (another batch size, another frame count, a re-planned or
+ * another handle of the same network); it does NOT know the weights - the caller keeps records apart per weight set. */
+/* 0 before dv_unet_prepare. */
+uint64_t dv_unet_cond_signature(const dv_unet* u);
+/* After a dv_unet_set_cond (or binds) on the prepared schedule: copies rows[0..n) of the conditioning (repeats allowed) into n
+ * new records, out[0..n).  A record owns its device memory: it outlives dv_unet_prepare and dv_unet_destroy.  Waits for the
+ * device before and after its one gather launch (k_voice_gather): the records are complete on return.  DV_ERR_INVALID for a
+ * row outside the batch, DV_ERR_STATE for a row that has not been conditioned since prepare; nothing is returned then. */
+int dv_voice_capture(dv_unet* u, const int32_t* rows, int32_t n, dv_voice** out);
+/* Writes voices[i] into row rows[i] of the CURRENT schedule's persistent buffers: one scatter launch (k_voice_scatter) on
+ * `stream` for up to 192 rows (one more per further 192; the pairs travel in the launch's 3 KiB argument block), no allocation,
+ * no wait - capturable.  The buffers' addresses do
+ * not change, so a sampler graph captured on this schedule replays with the new voices as it is.  Rows not named keep their
+ * conditioning.  dv_unet_forward / dv_sampler_run need every row conditioned since prepare, by dv_unet_set_cond or by binds
+ * (DV_ERR_STATE otherwise).  DV_ERR_INVALID, before anything is launched and with nothing changed, for a row outside the
+ * batch, a row named twice, or a record whose signature is not dv_unet_cond_signature.  The records must stay alive until
+ * the launch has run (dv_voice_destroy waits for the device). */
+int dv_unet_bind_voices(dv_unet* u, const int32_t* rows, dv_voice* const* voices, int32_t n, void* stream);
+/* Which rows have been conditioned since prepare: flags[0..n), n = the schedule's batch (DV_ERR_INVALID otherwise).  set = 0
+ * reads them; set != 0 overwrites them - a caller that used the schedule's rows as scratch for a conditioning pass of its own
+ * (re-deriving records) hands back the truth, and a forward is refused again while a row is unconditioned.  Host only. */
+int dv_unet_cond_rows(dv_unet* u, uint8_t* flags, int32_t n, int32_t set);
+uint64_t dv_voice_signature(const dv_voice* v);
+/* Device bytes of the record: every segment's bytes per utterance, i.e. it grows with L and not with B or T.  The production
+ * denoiser at L = 256 keeps 10 226 688 bytes (9.75 MiB) per voice, nearly all of it the K / V^T fragment planes of the 16 blocks:
+ * a service that enrols many voices budgets device memory for them. */
+int64_t dv_voice_bytes(const dv_voice* v);
+void dv_voice_destroy(dv_voice* v);
 
 /* ---- sampler: DPM-Solver++ / UniPC multistep loops --------------------------------- */
 
