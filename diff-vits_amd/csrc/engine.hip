@@ -593,6 +593,23 @@ struct Builder {
            B * Tn >= chain_min_rows &&
            G > 0 && G <= 64 && (G & (G - 1)) == 0 && C % G == 0 && (C / G) % 16 == 0 && (Tn / 32) * (C / 16) <= (C / 128) * 2048;
   }
+  // A C = 512 block (the mid block: 8 heads of d = 64) has no row-block chain, but its head and its self-attention tail run as the
+  // column-split launches of 32-row blocks (k_qkv_split<512, 0 / 1>, kernels_qkv.hip) under the conditions of the C = 384 ones:
+  // parity precision, hand-overs allowed, one round of at least qkv_split_min_wg workgroups, autotune off.  Decided BEFORE the
+  // block's producer is planned (it then writes block statistics instead of finishing the GroupNorm in its epilogue); whether the
+  // exchange words still fit is checked when the block itself is planned (transformer()).
+  int split32_wgs(int Tn, int C) const { ChainParams cp{}; cp.M = B * Tn; cp.C = C; return qkv_split_flags(cp); }
+  bool split32_ok(int Tn, int C) const {
+    const int G = u->cfg.norm_num_groups, H = u->cfg.num_heads;
+    if (C != 512 || C > qkv_split_max_c || C < qkv_split_min_c || !chain_on || !fuse_ln || arena.exact || prec != DV_PREC_BF16X3) return false;
+    if (!attn_frag_on || H <= 0 || C % H != 0 || (C / H) % 16 != 0 || C / H > 64) return false;
+    if (!handover_ok() || autotune_on() || Tn % 32 != 0) return false;
+    if (!(G > 0 && G <= 64 && (G & (G - 1)) == 0 && C % G == 0 && (C / G) % 16 == 0 && (Tn / 32) * (C / 16) <= 4096)) return false;
+    const int n_wg = split32_wgs(Tn, C);
+    return n_wg <= n_cu && n_wg >= qkv_split_min_wg;
+  }
+  // the block reads its input's 32x16 block statistics and normalises it itself (a row-block chain or the column-split head)
+  bool xf_own_norm(int Tn, int C) const { return chain_ok(Tn, C) || split32_ok(Tn, C); }
   // fragment-major copies of a packed weight (kernels_chain.hip k_relayout_frag), made once per prepare
   bool frag(const PackedW* cw) {
     if (dry) return true;
@@ -696,7 +713,7 @@ struct Builder {
   // ... a Transformer2DModel's own GroupNorm (eps 1e-6, no activation; reference transformer_1d.py:262) when its first GEMM runs
   // as a launch of its own (channel counts the row-block chain does not take)
   void announce_transformer_norm(const std::string& tp, int Tp, int C) {
-    if (chain_ok(Tp, C)) return;
+    if (xf_own_norm(Tp, C)) return;
     announce_norm(tp + "norm", false);
     next_norm.eps = 1e-6f; next_norm.silu = false;
   }
@@ -748,6 +765,10 @@ struct Builder {
   int qkv_split_min_wg = [] { const char* e = getenv("DVITS_QKV_SPLIT_MIN_WG"); return e ? atoi(e) : 96; }();
   // (at C = 128 a workgroup of the 32-row chain streams 0.26 MB of weights: nothing to save - 18.1 us against 19.3 us on the split launch)
   int qkv_split_min_c = [] { const char* e = getenv("DVITS_QKV_SPLIT_MIN_C"); return e ? atoi(e) : 256; }();
+  // (C = 512 - the mid block - runs the 32-row geometry of the same kernel; DVITS_QKV_SPLIT_MAX_C=384 restores its one launch per
+  // GEMM and the converting self attention.  There is no row-block chain at C = 512 to go back to: DVITS_QKV_SPLIT=0 does not
+  // reach this block)
+  int qkv_split_max_c = [] { const char* e = getenv("DVITS_QKV_SPLIT_MAX_C"); return e ? atoi(e) : 512; }();
   bool qkv_xa_on = [] { const char* e = getenv("DVITS_QKV_XA"); return !(e && e[0] == '0'); }();   // the cross-attention chains on k_qkv_split (MODE 2)
   // (C = 128: eight (head, row fragment) jobs walk all eight key tiles one after the other - 20 k cycles of key loop, 27.7 us against 24.2 us on the chain)
   int qkv_xa_min_c = [] { const char* e = getenv("DVITS_QKV_XA_MIN_C"); return e ? atoi(e) : 256; }();
@@ -1099,7 +1120,7 @@ struct Builder {
   }
   void ln_release(LnIn& in) { release(in.pl); if (in.stat) release(in.stat); }
 
-  // One k_qkv_split launch (kernels_qkv.hip: 64-row blocks, the output columns of the chain's contractions split over C / 64
+  // One k_qkv_split launch (kernels_qkv.hip: 64-row blocks - 32-row blocks at C = 512 -, the output columns of the chain's contractions split over C / 64
   // workgroups, hand-overs through exchange words inside the launch).  The caller has checked its own conditions and that the
   // words fit; false (nothing planned) if the kernel does not take `cp`.
   bool qkv_split(std::vector<OpFn>& ops, ChainParams cp, std::string desc, double extra_flops = 0.0) {
@@ -1152,10 +1173,14 @@ struct Builder {
 
     float* h3 = nullptr;
     LnIn l3;
-    if (chain_ok(b.Tp, C) && x.stat16) {
+    // (C = 512: both split launches' exchange words must still fit the pool - else one launch per GEMM, the GroupNorm by k_gn_apply)
+    const bool split32 = !chain_ok(b.Tp, C) && split32_ok(b.Tp, C) &&
+                         gnx_used + 2 * (((size_t)split32_wgs(b.Tp, C) + 1) & ~(size_t)1) <= dv_unet::GNX_POOL;
+    if ((chain_ok(b.Tp, C) || split32) && x.stat16) {
       if (!(frag(b.w_in) && frag(b.w_qkv) && frag(b.w_o1) && frag(b.w_q2))) return Act{};
       float* h = nullptr;
       const Planes ao = xf_head(ops, b, h);
+      if (!ao.hi) return Act{};
       if (!xf_tail(ops, b, h, ao, h3, l3)) return Act{};
     } else h3 = xf_attention_gemms(ops, b, l3);
     return xf_ff(ops, b, h3, l3, want_planes);
@@ -1189,9 +1214,14 @@ struct Builder {
     // kernels_qkv.hip: an all-gather of h inside the launch - planned like k_ff_split's hand-over; DVITS_QKV_SPLIT=0: the
     // 32-row chain above) wherever that gives the launch at least qkv_split_min_wg workgroups
     const int n_qflags = qkv_split_flags(cp);
-    const bool split = qkv_split_on && C >= qkv_split_min_c && sa_frag && handover_ok() && !autotune_on() &&
+    const bool chained = chain_ok(Tp, C);            // (C = 512: no row-block chain - transformer() has checked split32_ok)
+    // (descriptions: "(n wg / 64 rows)" marks the launches DVITS_QKV_SPLIT switches against a chain - the tests and tools count them
+    // by it; the C = 512 launches, which that switch does not reach, read "[n wg / 32 rows]")
+    const int q_rows = M * (C / 64) / n_qflags;      // rows of a row block (64; 32 at C = 512)
+    const bool split = (qkv_split_on || !chained) && C >= qkv_split_min_c && C <= qkv_split_max_c && sa_frag && handover_ok() && !autotune_on() &&
                        n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL &&   // (one round of workgroups: at B = 16 - 384 / 512 of them - the 32-row chain is the faster one, 4.09 vs 4.19 ms per forward)
-                       qkv_split(ops, cp, strf("norm+proj_in+LN+q|Kfrag|Vfrag (%d wg / 64 rows) M=%d C=%d N2=%d", C / 64, M, C, 3 * C));
+                       qkv_split(ops, cp, strf(chained ? "norm+proj_in+LN+q|Kfrag|Vfrag (%d wg / %d rows) M=%d C=%d N2=%d" : "norm+proj_in+LN+q|Kfrag|Vfrag [%d wg / %d rows] M=%d C=%d N2=%d", C / 64, q_rows, M, C, 3 * C));
+    if (!split && !chained) { err = "the column-split block head refused a shape its planner admitted"; return Planes{}; }
     if (!split) chain(ops, cp, sa_frag ? "norm+proj_in+LN+q|Kfrag|Vfrag" : "norm+proj_in+LN+qkv");
     probe(b.p + "proj_in", h, Tn, C);
     Planes ao;
@@ -1237,12 +1267,19 @@ struct Builder {
     }
     // (the same 64-row column-split launch as the block head - k_qkv_split, MODE 1: one round of workgroups)
     const int n_qflags = qkv_split_flags(cp);
-    const bool split = qkv_split_on && C >= qkv_split_min_c && handover_ok() && !autotune_on() &&
+    const bool chained = chain_ok(b.Tp, C);          // (C = 512: no row-block chain - the 32-row split launch, or one launch per GEMM)
+    const int q_rows = M * (C / 64) / n_qflags;
+    const bool split = (qkv_split_on || !chained) && C >= qkv_split_min_c && C <= qkv_split_max_c && handover_ok() && !autotune_on() &&
                        n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL &&
-                       qkv_split(ops, cp, strf("to_out+res+LN+to_q (%d wg / 64 rows) M=%d C=%d N2=%d", C / 64, M, C, C));
-    if (!split) chain(ops, cp, "to_out+res+LN+to_q");
-    release(ao); release(h);
-    probe(b.tb + "attn1", h2, b.Tn, C);
+                       qkv_split(ops, cp, strf(chained ? "to_out+res+LN+to_q (%d wg / %d rows) M=%d C=%d N2=%d" : "to_out+res+LN+to_q [%d wg / %d rows] M=%d C=%d N2=%d", C / 64, q_rows, M, C, C));
+    if (!split && !chained) {
+      release(q2); release(h2);
+      q2 = xf_out1_q2(ops, b, h, ao, h2);
+    } else {
+      if (!split) chain(ops, cp, "to_out+res+LN+to_q");
+      release(ao); release(h);
+      probe(b.tb + "attn1", h2, b.Tn, C);
+    }
     h3 = cross_attention_out(ops, b, q2, h2, l3);
     return true;
   }
@@ -1327,7 +1364,14 @@ struct Builder {
     ln_release(l1);
     Planes ao = attention(ops, qkv, 3 * C, qkv + C, qkv + 2 * C, 3 * C, nullptr, Tp, Tn, C, Tp);   // (keys: the frames that exist)
     release(qkv);
-    float* h2 = alloc((size_t)M * C);
+    float* h2 = nullptr;
+    float* q2 = xf_out1_q2(ops, b, h, ao, h2);
+    return cross_attention_out(ops, b, q2, h2, l3);
+  }
+  // attn1.to_out + residual h -> h2 -> LN2 -> attn2.to_q as one launch per GEMM; returns the query.  Consumes h and ao.
+  float* xf_out1_q2(std::vector<OpFn>& ops, const Xf& b, float* h, Planes ao, float*& h2) {
+    const int C = b.C, Tn = b.Tn, M = b.M;
+    h2 = alloc((size_t)M * C);
     LnIn l2;
     {
       GemmParams g = gp_base(Tn, M, C); g.seg[0] = seg(ao, C, Planes{}, 0, 1, 0);
@@ -1343,7 +1387,7 @@ struct Builder {
       g.out = q2; ln_consume(ops, g, l2, h2, b.w_q2, M, C); gemm(ops, g, b.w_q2, C);
     }
     ln_release(l2);
-    return cross_attention_out(ops, b, q2, h2, l3);
+    return q2;
   }
   // cross-attention (K/V hoisted: projected once per set_cond) of the query q2, then to_out + residual h2 -> h3 (returned) and
   // its LN3 partials l3.  Consumes q2 and h2.
@@ -1779,7 +1823,7 @@ struct Builder {
         if (!attn && !next_rp.empty()) announce_resnet(next_rp);
         if (attn) announce_transformer_norm(bp + "attentions." + std::to_string(j) + ".", h.Tp, c.block_out_channels[i]);
         Act r = resnet(S, bp + "resnets." + std::to_string(j) + ".", h, Act{}, c.block_out_channels[i], feeds_resampler && !attn,
-                       attn && chain_ok(h.Tp, c.block_out_channels[i]));
+                       attn && xf_own_norm(h.Tp, c.block_out_channels[i]));
         next_norm.set = false;
         if (!r.p) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
         if (attn) {
@@ -1803,7 +1847,7 @@ struct Builder {
     }
     {
       announce_transformer_norm("mid_block.attentions.0.", h.Tp, h.C);
-      Act r0 = resnet(S, "mid_block.resnets.0.", h, Act{}, h.C, false, chain_ok(h.Tp, h.C));
+      Act r0 = resnet(S, "mid_block.resnets.0.", h, Act{}, h.C, false, xf_own_norm(h.Tp, h.C));
       next_norm.set = false;
       if (!r0.p) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
       announce_resnet("mid_block.resnets.1.");
@@ -1829,7 +1873,7 @@ struct Builder {
         if (final_op && !attn) announce_norm("conv_norm_out", false);
         if (j < lpb && !attn) announce_up(i, j + 1);
         if (attn) announce_transformer_norm(bp + "attentions." + std::to_string(j) + ".", h.Tp, cout);
-        Act r = resnet(S, bp + "resnets." + std::to_string(j) + ".", h, sk, cout, feeds_resampler && !attn, attn && chain_ok(h.Tp, cout));
+        Act r = resnet(S, bp + "resnets." + std::to_string(j) + ".", h, sk, cout, feeds_resampler && !attn, attn && xf_own_norm(h.Tp, cout));
         next_norm.set = false;
         if (!r.p) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
         release_act(h);

@@ -1,8 +1,8 @@
-// Head of a transformer block at C = 128 / 256 / 384 for gfx950 (MI355X) as ONE launch of 64-row blocks whose COLUMNS are split over
+// Head of a transformer block at C = 128 / 256 / 384 / 512 for gfx950 (MI355X) as ONE launch of 64-row blocks (C = 512: 32-row) whose COLUMNS are split over
 // the workgroups: GroupNorm -> proj_in -> LayerNorm1 -> to_q | to_k | to_v (reference unet1d/transformer_1d.py:262-268: norm, proj_in;
 // attention.py:157-160: norm1, attn1's projections) - the work of k_chain2<NS, 1, false, true> (kernels_chain.hip, "chain 1"), same
 // ChainParams, same results layout (h fp32, q fp32, K / V^T as MFMA fragments of 32-key tiles).  The same launch form also runs the
-// two tails of the self attention (template parameter MODE, below): attn1.to_out + residual -> LN2 -> attn2.to_q (MODE 1, C = 384) and
+// two tails of the self attention (template parameter MODE, below): attn1.to_out + residual -> LN2 -> attn2.to_q (MODE 1, C = 384 / 512) and
 // the whole cross-attention chain ... -> cross attention -> attn2.to_out + residual -> LN3 partials (MODE 2, C = 256: the slice's heads
 // attend inside the launch, the attention output is a second hand-over).
 //
@@ -23,6 +23,17 @@
 // stream anyway: ChainParams out1), raises one flag word, waits for the flags of its row block (C / 64 consecutive workgroup ids:
 // gemm_handover_rounds, kernels_gemm.hip; bounded and flagged like every in-launch hand-over) and reads the 64 x C rows back - fp32,
 // so that LayerNorm1's row statistics are formed from exactly the values the reference normalises.
+//
+// Second geometry: 32-row blocks at C = 512 (the mid block: 8 heads of d = 64; QGeom<C>::RB = qrows(C)).  Two planes of 64 resident
+// rows (2 x 64 KiB) + an exchange region + the static LDS do not fit 160 KiB; 32 rows do (2 x 32 KiB + 32 KiB + 5 KiB).  The price is
+// ONE row fragment per weight fragment (three MFMAs per 16-byte weight unit instead of six); what is kept is the column split - a
+// workgroup streams 4 C x 64 x 4 = 0.5 MB of weights, not the 4 MB of all four matrices - and one round of workgroups at the bench
+// shape (M = 1024: 32 row blocks x 8 slices = 256).  Everything else is the 64-row code with the row-fragment count as a constant:
+// sixteen threads per row in the row passes (pieces 256 bytes apart), the k-quarter exchange of the one row fragment in one round,
+// MODE 1's LDS-DMA as (chunk, 8 rows) instructions shared out over (wave & 3, chunks of the wave's parity).  The hand-over is the
+// same one: same flags (XCC id inside), same bounded polls, same XCD-local form for whole multiples of 8 row blocks, and a row pitch
+// of whole 32-row blocks is what every padded row space has - utterances of any length run it.  MODE 0 and MODE 1 only (MODE 2's
+// jobs are (head, row fragment) pairs of 64-row blocks with d <= 32).  The C <= 384 instantiations compute what they computed.
 #include "dv_common.h"
 #include "dv_device.h"
 
@@ -52,27 +63,35 @@ extern "C" int dv_debug_qkv_trace(unsigned long long* host, int n_wg) {
 
 namespace {
 
-constexpr int NWV = 8, NT = 64 * NWV, BM = 64, BN = 64;
-constexpr int CHP = BM * 128;                        // bytes of one 64-channel chunk of one plane of the resident rows
+constexpr int NWV = 8, NT = 64 * NWV, BM = 64, BN = 64;   // (BM: the 64-row geometry - the only one MODE 2 runs at)
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ unsigned pk(float lo, float hi) { return dv_cvt_pk_bf16(lo, hi); }
 struct BFrag { bf16x8 h, l; };
 
-template <int C>
+// rows of a row block: 64 where two planes of 64 resident rows and an exchange region fit the LDS (C <= 384), 32 at C = 512
+constexpr int qrows(int c) { return c <= 384 ? 64 : 32; }
+template <int C, int ROWS = qrows(C)>
 struct QGeom {
+  static constexpr int RB = ROWS, NRF = RB / 32;     // rows of a row block, its 32-row fragments (row fragments per weight fragment)
+  static constexpr int CHP = RB * 128;               // bytes of one 64-channel chunk of one plane of the resident rows
+  static constexpr int TPR = NT / RB;                // threads per row in the row passes (8 / 16)
   static constexpr int NSPL = C / BN;                // workgroups per row block
   static constexpr int KS = C / 16, U = KS / 4;      // 16-deep k-steps of a contraction (K = C), per k-quarter (wave)
   static constexpr int DEPTH = U < 6 ? U : 6;        // weight units (hi + lo fragment: 8 VGPRs) in flight per wave
   static constexpr int A_CH = C / 64, A_PL = A_CH * CHP;
-  // k-quarter exchange: [column fragment][quarter][row fragment][register group][64 lanes] float4 - both row fragments at once
-  // (64 KiB) where the resident rows leave room (C <= 256), one row fragment per round (32 KiB) at C = 384
-  static constexpr bool ONE = 2 * A_PL + 65536 + 8192 <= 160 * 1024;
-  static constexpr int RED = ONE ? 65536 : 32768;
+  // k-quarter exchange: [column fragment][quarter][row fragment][register group][64 lanes] float4 - all row fragments at once
+  // (64 KiB; 32 KiB of a 32-row block) where the resident rows leave room (C <= 256, C = 512), one row fragment per round
+  // (32 KiB) at C = 384
+  static constexpr bool ONE = 2 * A_PL + NRF * 32768 + 8192 <= 160 * 1024;
+  static constexpr int RED = ONE ? NRF * 32768 : 32768;
   static constexpr int SMEM = 2 * A_PL + RED;
   static constexpr int D3 = 3 * U < 9 ? 3 * U : 9;   // weight units in flight per wave in the merged q | k | v loop
-  static constexpr int JT = C / 32;                  // float4 pieces of a row per thread (thread = (row, eighth): 8 threads per row)
+  static constexpr int JT = C / (4 * TPR);           // float4 pieces of a row per thread (thread = (row, part): TPR threads per row)
   static constexpr int ENT_MAX = RED / 8;            // GroupNorm block-statistics entries of one utterance that fit the exchange region
+  static constexpr int NRG = RB / 8;                 // MODE 1: 8-row groups of a chunk (one LDS-DMA instruction each), chunks per wave
+  static constexpr int DMA_CH = A_CH * NRG / NWV;
   static_assert(C % 128 == 0 && KS % 4 == 0 && SMEM + 8192 <= 160 * 1024, "geometry");
+  static_assert((RB == 32 || RB == 64) && NWV % NRG == 0 && (A_CH * NRG) % NWV == 0 && JT * 4 * TPR == C, "row passes");
 };
 
 // MODE 0: the block head (GroupNorm of the fp32 rows -> proj_in -> LN1 -> q | K | V fragments; ChainParams amode 1 with sa_*).
@@ -85,7 +104,7 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   char* const a_reg = smem;                          // the resident rows: [2 planes][C / 64 chunks][64 rows][128 B]
   char* const red_reg = smem + 2 * G::A_PL;          // k-quarter exchange; the utterance's GroupNorm entries before stage 1
   __shared__ __attribute__((aligned(16))) float s_gscale[C], s_gshift[C];
-  __shared__ __attribute__((aligned(16))) float2 s_ln[BM];   // per row (mean, rstd) of h
+  __shared__ __attribute__((aligned(16))) float2 s_ln[G::RB];   // per row (mean, rstd) of h
   // (every 64-byte line of the argument block is requested at once: see k_gemm)
   asm volatile("" ::"s"(p.M), "s"(p.gamma), "s"(p.w1_lo), "s"(p.out1), "s"(p.u2), "s"(p.sa_kf_hi), "s"(p.sa_vf_lo), "s"(p.qs_flags));
   DV_QTRACE(0);
@@ -101,11 +120,12 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   int rb, s;
   if (xl) { const int x = (int)blockIdx.x & 7, i = (int)blockIdx.x >> 3, rbl = i / G::NSPL; s = i - rbl * G::NSPL; rb = rbl * 8 + x; }
   else { rb = (int)blockIdx.x / G::NSPL; s = (int)blockIdx.x - rb * G::NSPL; }
-  const int m0 = rb * BM;
+  const int m0 = rb * G::RB;
   unsigned xcc = 0;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
   xcc &= 0xfu;
-  const int r_row = tid >> 3, r_e8 = tid & 7;        // row pass role: row of the block, eighth of its float4 pieces (coalesced: 8 lanes = 128 bytes)
+  constexpr int CHP = G::CHP, NRF = G::NRF, TPR = G::TPR;
+  const int r_row = tid / TPR, r_e8 = tid & (TPR - 1);   // row pass role: row of the block, part of its float4 pieces (coalesced: 8 lanes = 128 bytes)
 
   // weight unit j of this wave for column fragment nf (fragment-major [nf][k-step][64 lanes][8])
   auto load_unit = [&](const bf16_t* wf_hi, const bf16_t* wf_lo, int nf, int j) {
@@ -123,24 +143,24 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   };
   // one 64 x 64 tile over the resident rows: acc[rf] += W[nf][k-quarter kq] x A^T[row fragment rf] (SWAP: the rows are the first
   // operand - the accumulator is then the tile itself: lane = output column, registers = rows 8g + 4lh + e; used for V)
-  f32x16 acc[2];
+  f32x16 acc[NRF];
   auto job_loop = [&](const bf16_t* wf_hi, const bf16_t* wf_lo, int nf, auto swap_tag) __attribute__((always_inline)) {
     constexpr bool SWAP = decltype(swap_tag)::value;
 #pragma unroll
-    for (int rf = 0; rf < 2; ++rf)
+    for (int rf = 0; rf < NRF; ++rf)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[rf][r] = 0.f;
-    auto read_a = [&](int u, bf16x8 (&h)[2], bf16x8 (&l)[2]) {
+    auto read_a = [&](int u, bf16x8 (&h)[NRF], bf16x8 (&l)[NRF]) {
       const int c16 = (kq * G::U + u) * 2 + lh;      // 16-byte piece of the row: k-step * 2 + half
 #pragma unroll
-      for (int rf = 0; rf < 2; ++rf) {
+      for (int rf = 0; rf < NRF; ++rf) {
         const int row = rf * 32 + l31;
         const int off = (c16 >> 3) * CHP + row * 128 + (((c16 & 7) ^ swz(row)) << 4);
         h[rf] = *reinterpret_cast<const bf16x8*>(a_reg + off);
         l[rf] = *reinterpret_cast<const bf16x8*>(a_reg + G::A_PL + off);
       }
     };
-    bf16x8 ah[2][2], al[2][2];
+    bf16x8 ah[2][NRF], al[2][NRF];
     read_a(0, ah[0], al[0]);
 #pragma unroll
     for (int u = 0; u < G::U; ++u) {
@@ -148,19 +168,19 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
       if (u + 1 < G::U) read_a(u + 1, ah[cur ^ 1], al[cur ^ 1]);
       const BFrag f = bq[u % G::DEPTH];
       if (SWAP) {
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][0], f.h, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][1], f.h, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][0], f.l, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][1], f.l, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][0], f.h, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][1], f.h, acc[1], 0, 0, 0);
+#pragma unroll
+        for (int rf = 0; rf < NRF; ++rf) acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][rf], f.h, acc[rf], 0, 0, 0);
+#pragma unroll
+        for (int rf = 0; rf < NRF; ++rf) acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][rf], f.l, acc[rf], 0, 0, 0);
+#pragma unroll
+        for (int rf = 0; rf < NRF; ++rf) acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][rf], f.h, acc[rf], 0, 0, 0);
       } else {
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, al[cur][0], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, al[cur][1], acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l, ah[cur][0], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l, ah[cur][1], acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, ah[cur][0], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, ah[cur][1], acc[1], 0, 0, 0);
+#pragma unroll
+        for (int rf = 0; rf < NRF; ++rf) acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, al[cur][rf], acc[rf], 0, 0, 0);
+#pragma unroll
+        for (int rf = 0; rf < NRF; ++rf) acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l, ah[cur][rf], acc[rf], 0, 0, 0);
+#pragma unroll
+        for (int rf = 0; rf < NRF; ++rf) acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, ah[cur][rf], acc[rf], 0, 0, 0);
       }
       // pinned: without the scheduling barriers hipcc sinks every prefetch down to its use (load -> vmcnt(0) -> MFMA)
       __builtin_amdgcn_sched_barrier(0);
@@ -171,28 +191,32 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   // The four k-quarters are added through LDS (quarters in order: deterministic); wave (cf, fg) receives register group fg of
   // fragment cf for both row fragments: v[rf] = rows l31 x columns 8 fg + 4 lh + e of the fragment (SWAP: column l31 x rows ...)
   float4* const red4 = reinterpret_cast<float4*>(red_reg);
-  auto pieces = [&](const f32x16& a0, const f32x16& a1, float4 (&v)[2]) __attribute__((always_inline)) {
+  auto pieces = [&](const f32x16 (&a)[NRF], float4 (&v)[NRF]) __attribute__((always_inline)) {
+    const f32x16& a0 = a[0];
+    const f32x16& a1 = a[NRF - 1];
     if constexpr (G::ONE) {
       __syncthreads();                               // the exchange region is free; every wave has left the k-loop
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        red4[((((cf * 4 + kq) * 2 + 0) * 4 + g) << 6) + lane] = make_float4(a0[4 * g], a0[4 * g + 1], a0[4 * g + 2], a0[4 * g + 3]);
-        red4[((((cf * 4 + kq) * 2 + 1) * 4 + g) << 6) + lane] = make_float4(a1[4 * g], a1[4 * g + 1], a1[4 * g + 2], a1[4 * g + 3]);
+        red4[((((cf * 4 + kq) * NRF + 0) * 4 + g) << 6) + lane] = make_float4(a0[4 * g], a0[4 * g + 1], a0[4 * g + 2], a0[4 * g + 3]);
+        if constexpr (NRF == 2)
+          red4[((((cf * 4 + kq) * NRF + 1) * 4 + g) << 6) + lane] = make_float4(a1[4 * g], a1[4 * g + 1], a1[4 * g + 2], a1[4 * g + 3]);
       }
       __syncthreads();
 #pragma unroll
-      for (int rf = 0; rf < 2; ++rf) {
-        float4 t = red4[((((cf * 4 + 0) * 2 + rf) * 4 + fg) << 6) + lane];
+      for (int rf = 0; rf < NRF; ++rf) {
+        float4 t = red4[((((cf * 4 + 0) * NRF + rf) * 4 + fg) << 6) + lane];
 #pragma unroll
         for (int k = 1; k < 4; ++k) {
-          const float4 w = red4[((((cf * 4 + k) * 2 + rf) * 4 + fg) << 6) + lane];
+          const float4 w = red4[((((cf * 4 + k) * NRF + rf) * 4 + fg) << 6) + lane];
           t.x += w.x; t.y += w.y; t.z += w.z; t.w += w.w;
         }
         v[rf] = t;
       }
     } else {
+      static_assert(G::ONE || NRF == 2, "one row fragment per round: the 64-row geometry");
 #pragma unroll
-      for (int rf = 0; rf < 2; ++rf) {
+      for (int rf = 0; rf < NRF; ++rf) {
         __syncthreads();
 #pragma unroll
         for (int g = 0; g < 4; ++g)
@@ -211,7 +235,7 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   };
   // fp32 rows -> split planes of the resident operand: thread (r_row, r_e8) owns the float4 pieces 4 (r_e8 + 8 j) .. + 3 of its row
   auto put_planes = [&](int j, float v0, float v1, float v2, float v3) __attribute__((always_inline)) {
-    const int ch = 4 * (r_e8 + 8 * j);
+    const int ch = 4 * (r_e8 + TPR * j);
     uint2 hw, lw;
     hw.x = pk(v0, v1); hw.y = pk(v2, v3);
     lw.x = pk(v0 - __uint_as_float(hw.x << 16), v1 - __uint_as_float(hw.x & 0xffff0000u));
@@ -225,20 +249,23 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   float4 rv[G::JT];
   // bias of this lane's finished stage-1 columns (cold: requested at the head, not in front of its use)
   const float4 b1v = *reinterpret_cast<const float4*>(p.b1 + s * BN + cf * 32 + 8 * fg + 4 * lh);
-  float4 rres[2];                                    // MODE 1 / 2: the residual rows of this lane's finished pieces (cold: requested first)
-  float4 h2v[2];                                     // MODE 2: this lane's finished columns of x1 = to_out + residual (stage 3 adds them)
+  float4 rres[NRF];                                  // MODE 1 / 2: the residual rows of this lane's finished pieces (cold: requested first)
+  float4 h2v[NRF];                                   // MODE 2: this lane's finished columns of x1 = to_out + residual (stage 3 adds them)
   if constexpr (MODE >= 1) {
     const int ncol_ = s * BN + cf * 32 + 8 * fg + 4 * lh;
 #pragma unroll
-    for (int rf = 0; rf < 2; ++rf)
+    for (int rf = 0; rf < NRF; ++rf)
       rres[rf] = p.res ? *reinterpret_cast<const float4*>(p.res + (size_t)(m0 + rf * 32 + l31) * C + ncol_) : make_float4(0.f, 0.f, 0.f, 0.f);
     // the rows as split planes by LDS-DMA: instruction = (64-channel chunk, 8 rows) of one plane, wave w sends rows 8 w .. 8 w + 7
+    // of every chunk (32-row blocks: rows 8 (w & 3) .. + 7 of the chunks of its parity)
     const unsigned a_base = (unsigned)(size_t)a_reg;
-    const int d_row = wave * 8 + (lane >> 3), d_slot = lane & 7;
+    const int d_rg = G::NRG == NWV ? wave : wave % G::NRG, d_c0 = G::NRG == NWV ? 0 : wave / G::NRG;
+    const int d_row = d_rg * 8 + (lane >> 3), d_slot = lane & 7;
 #pragma unroll
-    for (int c = 0; c < G::A_CH; ++c) {
+    for (int i = 0; i < G::DMA_CH; ++i) {
+      const int c = d_c0 + i * (NWV / G::NRG);
       const size_t e = (size_t)(m0 + d_row) * C + c * 64 + ((d_slot ^ swz(d_row)) << 3);
-      const unsigned dst = a_base + (unsigned)(c * CHP + wave * 1024);
+      const unsigned dst = a_base + (unsigned)(c * CHP + d_rg * 1024);
       glds16(p.a_hi + e, dst);
       glds16(p.a_lo + e, dst + G::A_PL);
     }
@@ -251,7 +278,7 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   {
     const float* xr = p.x + (size_t)(m0 + r_row) * C + 4 * r_e8;
 #pragma unroll
-    for (int j = 0; j < G::JT; ++j) rv[j] = *reinterpret_cast<const float4*>(xr + 32 * j);
+    for (int j = 0; j < G::JT; ++j) rv[j] = *reinterpret_cast<const float4*>(xr + 4 * TPR * j);
   }
   job_prologue(p.w1_hi, p.w1_lo, s * 2 + cf);
   DV_QTRACE(10);
@@ -301,7 +328,7 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   }
 #pragma unroll
   for (int j = 0; j < G::JT; ++j) {
-    const int ch = 4 * (r_e8 + 8 * j);
+    const int ch = 4 * (r_e8 + TPR * j);
     const float4 sc = *reinterpret_cast<const float4*>(s_gscale + ch);
     const float4 sh = *reinterpret_cast<const float4*>(s_gshift + ch);
     put_planes(j, fmaf(rv[j].x, sc.x, sh.x), fmaf(rv[j].y, sc.y, sh.y), fmaf(rv[j].z, sc.z, sh.z), fmaf(rv[j].w, sc.w, sh.w));
@@ -317,16 +344,16 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   const int ncol = s * BN + cf * 32 + 8 * fg + 4 * lh;   // this lane's four columns of a finished piece (normal orientation)
   {
     const float4 b4 = b1v;
-    float4 pv[2];
-    pieces(acc[0], acc[1], pv);
+    float4 pv[NRF];
+    pieces(acc, pv);
 #pragma unroll
-    for (int rf = 0; rf < 2; ++rf) {
+    for (int rf = 0; rf < NRF; ++rf) {
       float4 v = pv[rf];
       v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
       if constexpr (MODE >= 1) {
-        const float4 r4 = rf == 0 ? rres[0] : rres[1];
+        const float4 r4 = rres[rf];
         v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
-        if (rf == 0) h2v[0] = v; else h2v[1] = v;      // (MODE 2: the residual of stage 3 - this lane's own columns of x1)
+        h2v[rf] = v;                               // (MODE 2: the residual of stage 3 - this lane's own columns of x1)
       }
       // the other workgroups of the row block read it back below (XCD-local: from the shared L2 - a plain store reaches it, the
       // L1 is write-through; else written through to memory), later launches read it as the residual stream
@@ -405,7 +432,16 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
     if (xl) {
       // L1-bypassing loads served by the XCD's L2, all of the row's pieces in flight behind ONE wait (the destination registers of an
       // asm load are only safe to read behind a wait inside the same block)
-      if constexpr (G::JT == 4)
+      if constexpr (TPR == 16) {
+        // (32-row blocks: sixteen threads per row, this thread's pieces 256 bytes apart)
+        static_assert(TPR == 8 || G::JT == 8, "sixteen threads per row: C = 512");
+        asm volatile("global_load_dwordx4 %0, %8, off sc1\n\tglobal_load_dwordx4 %1, %8, off offset:256 sc1\n\t"
+                     "global_load_dwordx4 %2, %8, off offset:512 sc1\n\tglobal_load_dwordx4 %3, %8, off offset:768 sc1\n\t"
+                     "global_load_dwordx4 %4, %8, off offset:1024 sc1\n\tglobal_load_dwordx4 %5, %8, off offset:1280 sc1\n\t"
+                     "global_load_dwordx4 %6, %8, off offset:1536 sc1\n\tglobal_load_dwordx4 %7, %8, off offset:1792 sc1\n\t"
+                     "s_waitcnt vmcnt(0)"
+                     : "=&v"(rv[0]), "=&v"(rv[1]), "=&v"(rv[2]), "=&v"(rv[3]), "=&v"(rv[4 % G::JT]), "=&v"(rv[5 % G::JT]), "=&v"(rv[6 % G::JT]), "=&v"(rv[7 % G::JT]) : "v"(hr) : "memory");
+      } else if constexpr (G::JT == 4)
         asm volatile("global_load_dwordx4 %0, %4, off sc1\n\tglobal_load_dwordx4 %1, %4, off offset:128 sc1\n\t"
                      "global_load_dwordx4 %2, %4, off offset:256 sc1\n\tglobal_load_dwordx4 %3, %4, off offset:384 sc1\n\t"
                      "s_waitcnt vmcnt(0)"
@@ -430,13 +466,14 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
                      : "v"(hr) : "memory");
     } else {
 #pragma unroll
-      for (int j = 0; j < G::JT; ++j) rv[j] = ld_handover16(hr + 8 * j);
+      for (int j = 0; j < G::JT; ++j) rv[j] = ld_handover16(hr + TPR * j);
     }
     // LayerNorm1 statistics of the row from the fp32 values (two passes over registers; 8 threads per row)
     float s1 = 0.f;
 #pragma unroll
     for (int j = 0; j < G::JT; ++j) s1 += (rv[j].x + rv[j].y) + (rv[j].z + rv[j].w);
     s1 += __shfl_xor(s1, 1); s1 += __shfl_xor(s1, 2); s1 += __shfl_xor(s1, 4);
+    if constexpr (TPR == 16) s1 += __shfl_xor(s1, 8);
     const float mean = s1 * (1.0f / (float)C);
     float m2 = 0.f;
 #pragma unroll
@@ -445,6 +482,7 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
       m2 = fmaf(d0, d0, m2); m2 = fmaf(d1, d1, m2); m2 = fmaf(d2, d2, m2); m2 = fmaf(d3, d3, m2);
     }
     m2 += __shfl_xor(m2, 1); m2 += __shfl_xor(m2, 2); m2 += __shfl_xor(m2, 4);
+    if constexpr (TPR == 16) m2 += __shfl_xor(m2, 8);
     if (r_e8 == 0) s_ln[r_row] = make_float2(mean, 1.0f / sqrtf(m2 * (1.0f / (float)C) + p.ln_eps));
     // (raw planes: LayerNorm's gamma / beta are folded into W2 / b2 / u2, its mean / rstd are applied in the epilogues)
 #pragma unroll
@@ -454,9 +492,9 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   DV_QTRACE(6);
 
   // ================= stage 2: the same 64 columns of q (MODE 0: and of k and of v) =================
-  auto finish_q = [&](const float4 (&pv)[2]) __attribute__((always_inline)) {     // fp32 [M, ldo2]
+  auto finish_q = [&](const float4 (&pv)[NRF]) __attribute__((always_inline)) {   // fp32 [M, ldo2]
 #pragma unroll
-    for (int rf = 0; rf < 2; ++rf) {
+    for (int rf = 0; rf < NRF; ++rf) {
       const float4 v = pv[rf];
       const float2 st = s_ln[rf * 32 + l31];
       float4 o;
@@ -467,8 +505,8 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   };
   if constexpr (MODE == 1) {
     job_loop(p.w2_hi, p.w2_lo, nfq, std::false_type{});
-    float4 pv[2];
-    pieces(acc[0], acc[1], pv);
+    float4 pv[NRF];
+    pieces(acc, pv);
     finish_q(pv);
     DV_QTRACE(7); DV_QTRACE(8); DV_QTRACE(9);
     return;
@@ -479,12 +517,12 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
     // C = 128 - one per wave - four at C = 256, two waves per job on the key tiles of either parity, merged through LDS.  The
     // arithmetic is k_chain2's (S^T = K Q^T and O^T += V^T P^T, split operands, scores in the log2 domain, online softmax lane-local).
     constexpr int d = C / 8, KSq = d / 16, HS = BN / d, KP = (2 * HS < NWV) ? 2 : 1;    // head dim, k-steps of a score, heads per slice, key-parity waves per job
-    static_assert(C <= 256 && 2 * HS * KP == NWV, "MODE 2 geometry");
+    static_assert(C <= 256 && 2 * HS * KP == NWV && G::RB == BM, "MODE 2 geometry");
     job_loop(p.w2_hi, p.w2_lo, nfq, std::false_type{});
     job_prologue(p.w3_hi, p.w3_lo, s * 2 + cf);      // the output projection's first weight fragments fly under the attention
     {
-      float4 pv[2];
-      pieces(acc[0], acc[1], pv);                    // (its barriers: every wave has left the k-loop - the rows of x1 are dead)
+      float4 pv[NRF];
+      pieces(acc, pv);                               // (its barriers: every wave has left the k-loop - the rows of x1 are dead)
       // the slice's queries, pre-scaled (d^-1/2 log2 e), as split planes in chunk 0 of the row region
 #pragma unroll
       for (int rf = 0; rf < 2; ++rf) {
@@ -659,12 +697,12 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
     // ================= stage 3: x3 = O W3^T + b3 + x1 -> fp32, raw planes and LayerNorm row partials (the GEGLU GEMM's inputs) =================
     job_loop(p.w3_hi, p.w3_lo, s * 2 + cf, std::false_type{});
     {
-      float4 pv[2];
-      pieces(acc[0], acc[1], pv);
+      float4 pv[NRF];
+      pieces(acc, pv);
       __shared__ float2 s_rp[2 * 32 * 2 * 4];        // [row][column fragment][register group] (sum, M2) of 8 columns
 #pragma unroll
       for (int rf = 0; rf < 2; ++rf) {
-        const float4 r4 = rf == 0 ? h2v[0] : h2v[1];
+        const float4 r4 = h2v[rf];
         float4 v = pv[rf];
         v.x += b3v.x + r4.x; v.y += b3v.y + r4.y; v.z += b3v.z + r4.z; v.w += b3v.w + r4.w;
         const size_t ob = (size_t)(m0 + rf * 32 + l31) * C + ncol;
@@ -703,23 +741,23 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   } else {
     // ONE k-loop for the three contractions: the row fragments of a k-step are read from LDS once and meet the q, the k and the v
     // fragment of this wave's columns (v with swapped operands: its accumulator is the transposed tile)
-    f32x16 aq[2], ak[2], av[2];
+    f32x16 aq[NRF], ak[NRF], av[NRF];
 #pragma unroll
-    for (int rf = 0; rf < 2; ++rf)
+    for (int rf = 0; rf < NRF; ++rf)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { aq[rf][r] = 0.f; ak[rf][r] = 0.f; av[rf][r] = 0.f; }
     {
-      auto read_a = [&](int u, bf16x8 (&h)[2], bf16x8 (&l)[2]) {
+      auto read_a = [&](int u, bf16x8 (&h)[NRF], bf16x8 (&l)[NRF]) {
         const int c16 = (kq * G::U + u) * 2 + lh;
 #pragma unroll
-        for (int rf = 0; rf < 2; ++rf) {
+        for (int rf = 0; rf < NRF; ++rf) {
           const int row = rf * 32 + l31;
           const int off = (c16 >> 3) * CHP + row * 128 + (((c16 & 7) ^ swz(row)) << 4);
           h[rf] = *reinterpret_cast<const bf16x8*>(a_reg + off);
           l[rf] = *reinterpret_cast<const bf16x8*>(a_reg + G::A_PL + off);
         }
       };
-      bf16x8 ah[2][2], al[2][2];
+      bf16x8 ah[2][NRF], al[2][NRF];
       read_a(0, ah[0], al[0]);
 #pragma unroll
       for (int j = 0; j < 3 * G::U; ++j) {
@@ -728,25 +766,25 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
         const BFrag f = b3[j % G::D3];
         if (ps == 2) {
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) av[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][rf], f.h, av[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) av[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][rf], f.h, av[rf], 0, 0, 0);
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) av[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][rf], f.l, av[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) av[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][rf], f.l, av[rf], 0, 0, 0);
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) av[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][rf], f.h, av[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) av[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][rf], f.h, av[rf], 0, 0, 0);
         } else if (ps == 1) {
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) ak[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, al[cur][rf], ak[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) ak[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, al[cur][rf], ak[rf], 0, 0, 0);
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) ak[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l, ah[cur][rf], ak[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) ak[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l, ah[cur][rf], ak[rf], 0, 0, 0);
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) ak[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, ah[cur][rf], ak[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) ak[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, ah[cur][rf], ak[rf], 0, 0, 0);
         } else {
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) aq[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, al[cur][rf], aq[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) aq[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, al[cur][rf], aq[rf], 0, 0, 0);
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) aq[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l, ah[cur][rf], aq[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) aq[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.l, ah[cur][rf], aq[rf], 0, 0, 0);
 #pragma unroll
-          for (int rf = 0; rf < 2; ++rf) aq[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, ah[cur][rf], aq[rf], 0, 0, 0);
+          for (int rf = 0; rf < NRF; ++rf) aq[rf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.h, ah[cur][rf], aq[rf], 0, 0, 0);
         }
         // pinned: without the scheduling barriers hipcc sinks every prefetch down to its use (load -> vmcnt(0) -> MFMA)
         __builtin_amdgcn_sched_barrier(0);
@@ -755,15 +793,15 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
       }
     }
     DV_QTRACE(7);
-    float4 pv[2];
+    float4 pv[NRF];
     // ---- q ----
-    pieces(aq[0], aq[1], pv);
+    pieces(aq, pv);
     finish_q(pv);
     // ---- k: K fragments of the two 32-key tiles of this block (lane (half, key) holds 8 channels of a 16-channel group; this
     //      lane's four at byte 8 lh - k_chain2's layout) ----
-    pieces(ak[0], ak[1], pv);
+    pieces(ak, pv);
 #pragma unroll
-    for (int rf = 0; rf < 2; ++rf) {
+    for (int rf = 0; rf < NRF; ++rf) {
       const float4 v = pv[rf];
       const float2 st = s_ln[rf * 32 + l31];
       const float o0 = st.y * (v.x - st.x * uk.x) + bk4.x, o1 = st.y * (v.y - st.x * uk.y) + bk4.y;
@@ -779,9 +817,9 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
     DV_QTRACE(8);
     // ---- v: lane = channel, registers = keys 8 fg + 4 lh + e: that register image is half of the lane's 16-byte piece of the V^T
     //      fragment (channel block, k-block fg >> 1) of the tile ----
-    pieces(av[0], av[1], pv);
+    pieces(av, pv);
 #pragma unroll
-    for (int rf = 0; rf < 2; ++rf) {
+    for (int rf = 0; rf < NRF; ++rf) {
       const float4 v = pv[rf];
       // (mean, rstd) of the four key rows rf * 32 + 8 fg + 4 lh + e: 32 contiguous bytes of s_ln
       const float4 s01 = *reinterpret_cast<const float4*>(&s_ln[rf * 32 + 8 * fg + 4 * lh]);
@@ -805,6 +843,12 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   }
 }
 
+// Do the slices of a row block share an XCD (hand-overs through its L2)?  Whole multiples of 8 row blocks; DVITS_QKV_XCD=0: never
+bool xcd_local_blocks(int row_blocks) {
+  static const bool xcd_on = [] { const char* e = getenv("DVITS_QKV_XCD"); return !(e && e[0] == '0'); }();
+  return xcd_on && row_blocks % 8 == 0;
+}
+
 template <int C>
 hipError_t qkv_init_one() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_split<C, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, QGeom<C>::SMEM);
@@ -817,9 +861,10 @@ hipError_t qkv_init_one() {
 template <int C>
 hipError_t qkv_launch_one(const ChainParams& pin, hipStream_t st) {
   ChainParams p = pin;
-  p.qs_xcd = qkv_split_xcd_local(p.M) ? 1 : 0;
-  if (p.amode == 1) hipLaunchKernelGGL((k_qkv_split<C, 0>), dim3((p.M / BM) * QGeom<C>::NSPL), dim3(NT), QGeom<C>::SMEM, st, p);
-  else if (!p.xa_kf_hi) hipLaunchKernelGGL((k_qkv_split<C, 1>), dim3((p.M / BM) * QGeom<C>::NSPL), dim3(NT), QGeom<C>::SMEM, st, p);
+  constexpr int RB = QGeom<C>::RB;
+  p.qs_xcd = xcd_local_blocks(p.M / RB) ? 1 : 0;
+  if (p.amode == 1) hipLaunchKernelGGL((k_qkv_split<C, 0>), dim3((p.M / RB) * QGeom<C>::NSPL), dim3(NT), QGeom<C>::SMEM, st, p);
+  else if (!p.xa_kf_hi) hipLaunchKernelGGL((k_qkv_split<C, 1>), dim3((p.M / RB) * QGeom<C>::NSPL), dim3(NT), QGeom<C>::SMEM, st, p);
   else {
     if constexpr (C <= 256) {
       if (!p.qs_xcd) return hipErrorInvalidValue;    // (the cross-attention form hands over through the XCD's L2 only)
@@ -831,22 +876,19 @@ hipError_t qkv_launch_one(const ChainParams& pin, hipStream_t st) {
 
 }  // namespace
 
-// Do the slices of a row block share an XCD (hand-overs through its L2)?  Whole multiples of 8 row blocks; DVITS_QKV_XCD=0: never
-bool qkv_split_xcd_local(int M) {
-  static const bool xcd_on = [] { const char* e = getenv("DVITS_QKV_XCD"); return !(e && e[0] == '0'); }();
-  return xcd_on && (M / BM) % 8 == 0;
-}
+bool qkv_split_xcd_local(int M) { return xcd_local_blocks(M / BM); }   // (the 64-row geometry: the cross-attention form asks)
 hipError_t qkv_split_init() {
   hipError_t e = qkv_init_one<128>();
   if (e == hipSuccess) e = qkv_init_one<256>();
-  return e != hipSuccess ? e : qkv_init_one<384>();
+  if (e == hipSuccess) e = qkv_init_one<384>();
+  return e != hipSuccess ? e : qkv_init_one<512>();
 }
 // chain 1 with its self-attention operands as fragments (amode 1, passes q | k | v, sa_*) or chain 2 without the cross attention
-// inside (amode 0, one pass), whole 64-row blocks per utterance
+// inside (amode 0, one pass), whole row blocks per utterance (64 rows; 32 at C = 512: a padded row space of any length has them)
 bool qkv_split_supported(const ChainParams& p, int precision) {
   if (precision != 0 || !p.out1 || (p.ldo2 & 3) != 0) return false;
-  if (p.C != 128 && p.C != 256 && p.C != 384) return false;
-  if (p.T % BM != 0 || p.M % p.T != 0 || p.Tv < 0 || p.Tv > p.T || (p.Tv > 0 && p.Tv <= p.T - 32)) return false;
+  if (p.C != 128 && p.C != 256 && p.C != 384 && p.C != 512) return false;
+  if (p.T % qrows(p.C) != 0 || p.M % p.T != 0 || p.Tv < 0 || p.Tv > p.T || (p.Tv > 0 && p.Tv <= p.T - 32)) return false;
   if (p.amode == 1) {
     if (p.passes != 3 || !p.sa_kf_hi || !p.sa_kf_lo || !p.sa_vf_hi || !p.sa_vf_lo || p.res || p.xa_kf_hi || !p.out2 || p.ldo2 < p.C) return false;
     const int G = p.groups;
@@ -854,13 +896,13 @@ bool qkv_split_supported(const ChainParams& p, int precision) {
     if ((p.T / 32) * (p.C / 16) > 2 * 4 * 4 * 64 * 16 / 8) return false;   // the utterance's GroupNorm entries fit the exchange region
     return true;
   }
-  if (p.amode != 0 || p.passes != 1 || !p.a_hi || !p.a_lo || p.sa_kf_hi) return false;
+  if (p.amode != 0 || p.passes != 1 || !p.a_hi || !p.a_lo || !p.res || p.sa_kf_hi) return false;
   if (!p.xa_kf_hi) return p.out2 && p.ldo2 >= p.C;                         // MODE 1: the query leaves as fp32
   // MODE 2: the cross attention inside (8 heads of d = C / 8 = 16 / 32, whole multiples of 8 row blocks: XCD-local hand-overs only)
   return p.C <= 256 && p.xa_kf_lo && p.xa_vf_hi && p.xa_vf_lo && p.xa_bias && p.xa_nT > 0 && p.xa_d == p.C / 8 && p.w3_hi && p.w3_lo && p.b3 &&
          p.out3 && p.out3_hi && p.out3_lo && p.rowstat3 && p.qs_o_hi && p.qs_o_lo && qkv_split_xcd_local(p.M);
 }
-int qkv_split_flags(const ChainParams& p) { return (p.M / BM) * (p.C / BN) * (p.xa_kf_hi ? 2 : 1); }   // (the cross-attention form hands over twice)
+int qkv_split_flags(const ChainParams& p) { return (p.M / qrows(p.C)) * (p.C / BN) * (p.xa_kf_hi ? 2 : 1); }   // (the cross-attention form hands over twice)
 hipError_t launch_qkv_split(const ChainParams& p, int precision, hipStream_t st) {
   if (!qkv_split_supported(p, precision)) return hipErrorInvalidValue;
   if ((p.amode == 1 && (!p.x || !p.stat16 || !p.gamma || !p.beta)) || !p.w1_hi || !p.w1_lo || !p.b1 || !p.w2_hi || !p.w2_lo || !p.b2 || !p.u2 ||
@@ -868,9 +910,10 @@ hipError_t launch_qkv_split(const ChainParams& p, int precision, hipStream_t st)
     return hipErrorInvalidValue;
   if (!gemm_handover_rounds()) {                     // (else: the wait is for C / 64 consecutive workgroup ids)
     static const int n_cu = [] { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
-    if ((p.M / BM) * (p.C / BN) > n_cu) return hipErrorInvalidValue;
+    if ((p.M / qrows(p.C)) * (p.C / BN) > n_cu) return hipErrorInvalidValue;
   }
   if (p.C == 128) return qkv_launch_one<128>(p, st);
   if (p.C == 256) return qkv_launch_one<256>(p, st);
-  return qkv_launch_one<384>(p, st);
+  if (p.C == 384) return qkv_launch_one<384>(p, st);
+  return qkv_launch_one<512>(p, st);
 }
