@@ -146,6 +146,7 @@ struct Act {   // channels-last fp32 [B*Tp, C] (+ GN statistics) (+ split planes
   float* stat = nullptr;      // per-column slab [B*T/32, C, 2] (consumer: k_gn_apply), or
   float* stat16 = nullptr;    // per 32x16-block statistics [B*T/32, C/16, 2] (consumer: a conv that normalises its own operand)
   bf16_t* pl_hi = nullptr; bf16_t* pl_lo = nullptr;
+  bool no_fp32 = false;       // the producer writes no fp32 copy (p stays unwritten): the tensor exists as the planes pl_hi / pl_lo alone
   // GroupNorm + SiLU of this tensor for ONE consumer (`n_pre` = its norm's weight prefix), written by the producer GEMM's
   // own epilogue (GnxParams); the consumer releases them
   bf16_t* n_hi = nullptr; bf16_t* n_lo = nullptr; std::string n_pre;
@@ -157,7 +158,8 @@ struct Act {   // channels-last fp32 [B*Tp, C] (+ GN statistics) (+ split planes
 typedef std::function<hipError_t(hipStream_t)> OpFn;
 
 // p: fp32 rows, Tp frames per utterance apart.  Split-plane tensors (p null): hi (+ lo, bf16x3) planes, joined on the host and
-// multiplied by `scale` (a factor the schedule folds into the consumer's weights)
+// multiplied by `scale` (a factor the schedule folds into the consumer's weights).  A tap (DVITS_KEEP_INTERMEDIATES=tap) has the same
+// form: its pointers are side buffers outside the arena, filled by a copy operation of the schedule
 struct Probe { std::string name; float* p; int T, C, Tp; const bf16_t* hi = nullptr; const bf16_t* lo = nullptr; float scale = 1.f; };
 
 struct dv_unet {
@@ -204,6 +206,9 @@ struct dv_unet {
   bool persist_on = false;
   double flops = 0;
   bool keep_intermediates = false;
+  // DVITS_KEEP_INTERMEDIATES=tap: the production plan (keep_intermediates stays false everywhere), every probe a copy operation
+  // behind its producer into a side buffer of its own (in `owned`)
+  bool tap_mode = false;
   // per-call I/O (read by the ops when they are enqueued)
   struct { const float* x = nullptr; int cx = 0; const float* cond = nullptr; const float* t = nullptr; float* y = nullptr;
            const float* enc = nullptr; const float* mask = nullptr;
@@ -461,7 +466,40 @@ struct Builder {
     return true;
   }
   void probe(const std::string& name, const float* p, int T_, int C_) {
-    if (!dry && u->keep_intermediates) u->probes.push_back(Probe{name, const_cast<float*>(p), T_, C_, T_ > 1 ? pitch(T_) : T_});
+    const int Tp_ = T_ > 1 ? pitch(T_) : T_;
+    if (!dry && u->keep_intermediates) u->probes.push_back(Probe{name, const_cast<float*>(p), T_, C_, Tp_});
+    if (!dry && u->tap_mode) tap(name, p, nullptr, nullptr, T_, C_, Tp_);
+  }
+  // ... of a tensor whose producer may have dropped the fp32 copy (an up-path tensor read through planes alone: offer_next)
+  void probe(const std::string& name, const Act& a) {
+    if (!a.no_fp32) { probe(name, a.p, a.T, a.C); return; }
+    if (!dry && u->tap_mode) tap(name, nullptr, a.pl_hi, a.pl_lo, a.T, a.C, a.Tp);
+  }
+  // A tap: the tensor the operation emitted last has written - fp32 rows, or its raw split planes - copied as it lies (padding
+  // rows included) into a side buffer outside the arena, by ONE operation of kind "probe" directly behind the producer.  The
+  // plan itself is the production one: nothing is allocated from the arena and no release is held back.
+  void tap(const std::string& name, const float* p, const bf16_t* hi, const bf16_t* lo, int T_, int C_, int Tp_) {
+    const size_t n = (size_t)B * Tp_ * C_;
+    void* side[2] = {nullptr, nullptr};
+    const void* src[2] = {p ? (const void*)p : (const void*)hi, p ? nullptr : (const void*)lo};
+    const size_t bytes = n * (p ? sizeof(float) : sizeof(bf16_t));
+    if (!src[0]) return;
+    for (int i = 0; i < 2; ++i) {
+      if (!src[i]) continue;
+      if (hipMalloc(&side[i], bytes) != hipSuccess) { if (err.empty()) err = "hipMalloc(tap " + name + ") failed"; return; }
+      u->owned.push_back(side[i]);
+    }
+    Probe pr{name, reinterpret_cast<float*>(p ? side[0] : nullptr), T_, C_, Tp_};
+    if (!p) { pr.hi = reinterpret_cast<const bf16_t*>(side[0]); pr.lo = reinterpret_cast<const bf16_t*>(side[1]); }
+    u->probes.push_back(pr);
+    void* d0 = side[0]; void* d1 = side[1];
+    const void* s0 = src[0]; const void* s1 = src[1];
+    cur_kind = "probe"; cur_flops = 0; cur_desc = name + (p ? "" : " (planes)");
+    emit(u->step_ops, [=](hipStream_t st) {
+      hipError_t e = hipMemcpyAsync(d0, s0, bytes, hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess && s1) e = hipMemcpyAsync(d1, s1, bytes, hipMemcpyDeviceToDevice, st);
+      return e;
+    });
   }
   // the prompt encoder's tensors are [B * L, C] with no row padding, whatever pitch() says of L (with n_levels = 0
   // stat16_everywhere() holds vacuously and pitch(L) would be rup(L, 32))
@@ -750,7 +788,7 @@ struct Builder {
     // (an up-path tensor has this one consumer, which reads it through the planes alone when its shortcut is a convolution)
     const bool fp32_unread = cat && nn.raw && !u->keep_intermediates;
     if (nn.raw && !prod.out_hi) out_planes(prod, out);   // the consumer's folded 1x1 shortcut reads the raw tensor as split planes
-    if (fp32_unread && cat_drop_fp32) prod.out = nullptr;
+    if (fp32_unread && cat_drop_fp32) { prod.out = nullptr; out.no_fp32 = true; }
   }
   // split planes of a producer's output [prod.M, out.C] beside its fp32 tensor (a resampling conv or a folded 1x1 shortcut reads them)
   template <class P> void out_planes(P& prod, Act& out) {
@@ -813,9 +851,10 @@ struct Builder {
     cur_kind = "gemm"; cur_flops = 2.0 * (double)g.M * (double)g.N * (double)k_real;
     {
       char buf[128];
-      snprintf(buf, sizeof(buf), "M=%d N=%d K=%d taps=%d nseg=%d epi=%d stride=%d up=%d%s%s%s", g.M, g.N, k_real, g.seg[0].taps,
+      // (" -fp32": no fp32 output - the tensor leaves as its raw planes, or, with no planes either, normalised only)
+      snprintf(buf, sizeof(buf), "M=%d N=%d K=%d taps=%d nseg=%d epi=%d stride=%d up=%d%s%s%s%s", g.M, g.N, k_real, g.seg[0].taps,
                g.nseg, g.epi, g.stride, g.up_mode, (g.stats || g.stats16) ? " +stats" : "", c3 ? " resident" : "",
-               g.gnx.xchg ? " +gnx" : "");
+               g.gnx.xchg ? " +gnx" : "", (g.gnx.xchg && !g.out) ? (g.out_hi ? " -fp32" : " -fp32 normonly") : "");
       cur_desc = buf;
     }
     u->flops += dry ? 0.0 : cur_flops;
@@ -1006,7 +1045,7 @@ struct Builder {
         if (n1b.hi) release(n1b);
       }
     }
-    probe(p + "conv1", h.p, Tn, cout);
+    if (!gnx1 || u->keep_intermediates) probe(p + "conv1", h.p, Tn, cout);   // (else h exists only normalised: nothing to tap)
 
     const int K2 = 3 * cout + (shortcut ? cin : 0);
     std::vector<Piece> pcs = {{p + "conv2.weight", 1, cout, 3, cout, 0, 0, "", 0}};
@@ -1035,7 +1074,7 @@ struct Builder {
     release_act(h);
     if (raw_made) release(raw);
     if (raw1.hi) release(raw1);
-    probe(p.substr(0, p.size() - 1), out.p, Tn, cout);
+    probe(p.substr(0, p.size() - 1), out);
     return out;
   }
 
@@ -1469,7 +1508,7 @@ struct Builder {
     if (want_planes) out_planes(fp, out);
     offer_next(fp, out);
     const double flops = 2.0 * (double)M * C * (8.0 * C + 5.0 * C);
-    const char* gnx = fp.gnx.xchg ? "+gnx" : "";
+    const char* gnx = fp.gnx.xchg ? (fp.out ? "+gnx" : "+gnx-fp32") : "";   // ("-fp32": the output leaves as planes alone)
     const int pr = prec;
     if constexpr (split) {
       emit_launch(ops, "chain", flops, strf("LN+GEGLU+ffproj+res%s (%d wg / %d rows) M=%d C=%d", gnx, fp.nspl, fp.rows, M, C),
@@ -1481,7 +1520,7 @@ struct Builder {
     }
     ln_release(l3);
     release(h3);
-    probe(b.p.substr(0, b.p.size() - 1), out.p, b.Tn, C);
+    probe(b.p.substr(0, b.p.size() - 1), out);
     return out;
   }
   // the feed-forward as GEMMs: GEGLU, then the merged ffproj GEMM or ff.net.2 and proj_out
@@ -1513,7 +1552,7 @@ struct Builder {
       }
       ln_release(l3);
       release(gg); release(h3);
-      probe(b.p.substr(0, b.p.size() - 1), out.p, Tn, C);
+      probe(b.p.substr(0, b.p.size() - 1), out);
       return out;
     }
     ln_release(l3);
@@ -1536,7 +1575,7 @@ struct Builder {
       gemm(ops, g, b.w_out, C);
     }
     release(h4);
-    probe(b.p.substr(0, b.p.size() - 1), out.p, Tn, C);
+    probe(b.p.substr(0, b.p.size() - 1), out);
     return out;
   }
 
@@ -1569,7 +1608,7 @@ struct Builder {
     offer_next(g, out);
     gemm(ops, g, w, 3 * C);
     release(xs);
-    probe(p.substr(0, p.size() - 1), out.p, T_new, C);
+    probe(p.substr(0, p.size() - 1), out);
     return out;
   }
 
@@ -2127,6 +2166,7 @@ extern "C" int dv_unet_prepare(dv_unet* u, int32_t B, int32_t T, int32_t L, int3
   u->B = B; u->T = T; u->L = L; u->precision = precision; u->force_up = force_upsample_size;
   const char* keep = getenv("DVITS_KEEP_INTERMEDIATES");
   u->keep_intermediates = keep && keep[0] == '1';
+  u->tap_mode = keep && strcmp(keep, "tap") == 0;   // (the plan of an unset variable + one copy operation per probe)
 
   const bool persist_env = [] { const char* e = getenv("DVITS_PERSIST"); return e && e[0] == '1'; }();
   // pass 1: measure the arena
@@ -2237,6 +2277,7 @@ extern "C" int dv_penc_prepare(dv_penc* p, int32_t B, int32_t L, int32_t precisi
   u->B = B; u->T = L; u->L = L; u->precision = precision; u->force_up = 0;
   const char* keep = getenv("DVITS_KEEP_INTERMEDIATES");
   u->keep_intermediates = keep && keep[0] == '1';
+  u->tap_mode = false;                               // (taps: the denoiser only)
   size_t need = 0;
   {
     Builder b{};
@@ -2669,10 +2710,14 @@ static int probe_copy(dv_unet* u, const char* name, float* host_out, int64_t cap
       if (!host_out) return DV_OK;
       if (capacity < n) return dv_fail(DV_ERR_INVALID, "probe buffer too small");
       HIPCHK(hipDeviceSynchronize());
-      if (!p.p) {   // split planes, unpadded rows: fp32 value = hi + lo (bf16 bits are the upper half of an fp32)
+      if (!p.p) {   // split planes: fp32 value = hi + lo (bf16 bits are the upper half of an fp32); B pieces of T frames, Tp frames apart
+        const size_t row = (size_t)p.T * p.C, pitch = (size_t)p.Tp * p.C;
         std::vector<bf16_t> h((size_t)n), l;
-        HIPCHK(hipMemcpy(h.data(), p.hi, (size_t)n * sizeof(bf16_t), hipMemcpyDeviceToHost));
-        if (p.lo) { l.resize((size_t)n); HIPCHK(hipMemcpy(l.data(), p.lo, (size_t)n * sizeof(bf16_t), hipMemcpyDeviceToHost)); }
+        HIPCHK(hipMemcpy2D(h.data(), row * sizeof(bf16_t), p.hi, pitch * sizeof(bf16_t), row * sizeof(bf16_t), (size_t)u->B, hipMemcpyDeviceToHost));
+        if (p.lo) {
+          l.resize((size_t)n);
+          HIPCHK(hipMemcpy2D(l.data(), row * sizeof(bf16_t), p.lo, pitch * sizeof(bf16_t), row * sizeof(bf16_t), (size_t)u->B, hipMemcpyDeviceToHost));
+        }
         auto f32 = [](bf16_t b) { const uint32_t w = (uint32_t)b << 16; float f; memcpy(&f, &w, 4); return f; };
         for (int64_t i = 0; i < n; ++i) host_out[i] = p.scale * (f32(h[(size_t)i]) + (p.lo ? f32(l[(size_t)i]) : 0.f));
         return DV_OK;
@@ -2683,7 +2728,8 @@ static int probe_copy(dv_unet* u, const char* name, float* host_out, int64_t cap
       return DV_OK;
     }
   }
-  return dv_fail(DV_ERR_INVALID, "no probe named %s (prepare with DVITS_KEEP_INTERMEDIATES=1)", name);
+  return dv_fail(DV_ERR_INVALID, "no probe named %s (prepare with DVITS_KEEP_INTERMEDIATES=1%s)", name,
+                 u->tap_mode ? "; the tapped production plan holds no such tensor" : "");
 }
 
 extern "C" int dv_unet_probe(dv_unet* u, const char* name, float* host_out, int64_t capacity, int64_t* dims) {

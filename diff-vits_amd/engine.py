@@ -690,7 +690,10 @@ class UNetEngine:
         return 1e3 * ms.value / n.value, n.value // reps
 
     def probe(self, name):
-        """Named intermediate [B, T, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1)."""
+        """Named intermediate [B, T, C] of the last forward.  Needs DVITS_KEEP_INTERMEDIATES at prepare time: `1` plans a schedule
+        of its own that keeps all 132 names (two-GEMM feed-forward, no buffer reuse); `tap` keeps the production plan and copies
+        each tensor out behind its producer (rows of kind "probe" in profile_forward name the taps) - `...transformer_blocks.0.ff`
+        and the `conv1` that exist only normalised are not registered there and raise like any unknown name."""
         dims = (C.c_int64 * 3)()
         _lib.check(_lib.lib().dv_unet_probe(self._h, name.encode(), None, 0, dims), "dv_unet_probe")
         out = torch.empty(tuple(dims), dtype=torch.float32)

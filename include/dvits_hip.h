@@ -186,10 +186,15 @@ int dv_unet_persist_ticks(dv_unet* u, int32_t* first_op, uint64_t* ticks, int32_
 
 /* Debug/parity probe: copy a named intermediate activation (channels-last [B, T, C]) of the
  * last forward to the host.  Available only when dv_unet_prepare ran with the environment
- * variable DVITS_KEEP_INTERMEDIATES=1 (buffers are then never reused).  dims[3] = {B, T, C};
+ * variable DVITS_KEEP_INTERMEDIATES=1 (buffers are then never reused) or =tap.  dims[3] = {B, T, C};
  * host_out may be NULL to query dims.  Names follow the reference module paths, e.g.
  * "conv_in", "emb", "down_blocks.0.resnets.0", "down_blocks.0.attentions.0",
- * "mid_block.resnets.1", "up_blocks.1.upsamplers.0". */
+ * "mid_block.resnets.1", "up_blocks.1.upsamplers.0".
+ * =1 plans a schedule of its own that keeps every intermediate (the feed-forward as two GEMMs, no buffer reuse, every fp32 copy
+ * kept).  =tap plans what an unset variable plans and adds one copy operation per probe (kind "probe" in dv_unet_op_info, counted
+ * by dv_unet_stats) behind its producer, into a side buffer freed with the schedule; a tensor without an fp32 copy is read from
+ * its split planes.  Names the production plan does not hold - "...transformer_blocks.0.ff", and a "...conv1" whose output exists
+ * only normalised - are not registered then: DV_ERR_INVALID, as for any unknown name. */
 int dv_unet_probe(dv_unet* u, const char* name, float* host_out, int64_t capacity, int64_t* dims);
 
 /* ---- enrolled voices: the conditioning of one speaker prompt, kept and bound to batch rows --------------------------------

@@ -273,3 +273,36 @@ def prompt_oracle_probes(sd, prompt, lengths, n_layers, num_heads=8):
     names = prompt_probe_names(n_layers)
     assert set(names) == set(out), set(names) ^ set(out)
     return y.permute(0, 2, 1).contiguous(), {n: out[n] for n in names}
+
+
+# ---- the one-launch feed-forward in isolation (tests/test_gpu_tapped_schedule.py, tests/test_ff_tail_reference.py) --------------
+FF_TAIL_BOUND = 1e-4        # whole tensor and every frame: test_conv3's bound for the same split-bf16 contraction
+
+
+def ff_tail_fp64(sd, p, h3, x, drop_ff=False, swap_geglu=False):
+    """What k_chain_ff / k_ff_split compute for the Transformer2DModel with prefix `p` ("....attentions.0."), restated in fp64 from
+    the UNMERGED state-dict weights:  proj_out(h3 + ff.net.2(GEGLU(ff.net.0(LN3(h3))))) + x,  h3 = the block after its cross
+    attention, x = the transformer's input, both channels-last [B, T, C].  `drop_ff` / `swap_geglu` plant a fault (the
+    feed-forward term left out; the value and gate halves of GEGLU exchanged) for the tests that show the bound has teeth."""
+    import torch.nn.functional as F
+    tb = p + "transformer_blocks.0."
+    W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
+    h3, x = torch.as_tensor(h3).to(torch.float64), torch.as_tensor(x).to(torch.float64)
+    C = h3.shape[-1]
+    n = F.layer_norm(h3, (C,), W(tb + "norm3.weight"), W(tb + "norm3.bias"), 1e-5)
+    a, gate = F.linear(n, W(tb + "ff.net.0.proj.weight"), W(tb + "ff.net.0.proj.bias")).chunk(2, dim=-1)
+    if swap_geglu:
+        a, gate = gate, a
+    ff = F.linear(a * F.gelu(gate), W(tb + "ff.net.2.weight"), W(tb + "ff.net.2.bias"))
+    h4 = h3 if drop_ff else h3 + ff
+    return F.linear(h4, W(p + "proj_out.weight")[:, :, 0], W(p + "proj_out.bias")) + x
+
+
+def seam_figures(per_frame, rows):
+    """Worst per-frame error of a [B, T] array, reported apart as test_conv3 does: the first frame, the last frame, the frames at
+    the seams of `rows`-high row blocks (multiples of `rows` and the frames just before them), every other frame."""
+    T = per_frame.shape[1]
+    seams = sorted({t for t in range(T) if t % rows in (0, rows - 1)} - {0, T - 1})
+    inner = sorted(set(range(T)) - set(seams) - {0, T - 1})
+    return {"first": float(per_frame[:, 0].max()), "last": float(per_frame[:, T - 1].max()),
+            "seams": float(per_frame[:, seams].max()) if seams else 0.0, "inner": float(per_frame[:, inner].max()) if inner else 0.0}

@@ -127,11 +127,14 @@ def test_every_block_per_frame_on_the_hot_path_kernels(case, B, T, L, env):
     from k_gemm: the convolutions on the convolution kernels and the k_qkv_split launches as _expected_plan derives them from the
     shape, fragment attention on every level with 16-channel head groups, row-block chains wherever a level has 128 rows.
 
-    DVITS_KEEP_INTERMEDIATES itself changes the plan in three places (csrc/engine.hip): ff.net.2 and proj_out stay two GEMMs
-    (merged_ffproj off - the `ff` probe exists only then), so k_ff_split / k_chain_ff are NOT planned; conv1 keeps its fp32
-    output although its consumer's GroupNorm is finished in the launch; an up-path tensor keeps its fp32 copy beside the
-    planes of the concatenated GroupNorm.  The one-launch feed-forward is therefore checked on a second engine without the
-    probes: its plan must hold the k_ff_split / k_chain_ff launches, and its OUTPUT goes through the same three criteria."""
+    DVITS_KEEP_INTERMEDIATES=1 itself changes the plan in six places (csrc/engine.hip): ff.net.2 and proj_out stay two GEMMs
+    (merged_ffproj off - the `ff` probe exists only then), so k_ff_split / k_chain_ff are NOT planned; the arena reuses no
+    buffer; conv1 keeps its fp32 output although its consumer's GroupNorm is finished in the launch; an up-path tensor keeps
+    its fp32 copy beside the planes of the concatenated GroupNorm; the batched timestep-embedding table is off; no buffer
+    shares its address with the production plan.  Here the one-launch feed-forward is therefore only checked on a second engine
+    without the probes: its plan must hold the k_ff_split / k_chain_ff launches, and its OUTPUT goes through the same three
+    criteria.  tests/test_gpu_tapped_schedule.py (DVITS_KEEP_INTERMEDIATES=tap) probes the production plan itself, layer by
+    layer, and compares each feed-forward launch alone with an fp64 restatement."""
     from diff_vits_amd import synth
     from diff_vits_amd.unet1d.unet_1d_condition import UNet1DConditionModel
     kw = UNET_CASES[case][0]
