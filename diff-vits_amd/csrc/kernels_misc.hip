@@ -109,8 +109,10 @@ hipError_t launch_gn_apply(const GnApplyParams& p, hipStream_t st) {
 // ---------------------------------------------------------------------------------------
 // GroupNorm statistics (reference F.group_norm calls: resnet.py:594,621; transformer_1d.py:257;
 // unet_1d_condition.py:1030) over the channel-concat [a0 | a1] of channels-last tensors.
-// Stage 1: per (batch, frame-chunk, group) partial sum / sum of squares, accumulated in
-// fp32 per thread (<= 64 values) and combined in fp64.  Stage 2 (k_gn_finalize) reduces the
+// Stage 1: per (batch, frame-chunk, group) partial sum / sum of squares, accumulated and
+// combined in fp64: var = E[x^2] - mean^2 cancels mean^2 / var of the sums' precision, which
+// fp32 sums of squares do not have at a group mean of many sigma (300 sigma: rstd was 9e-4
+// off; tests/test_gpu_ops.py test_group_stats_value_edges).  Stage 2 (k_gn_finalize) reduces the
 // chunks in fp64 and emits the per-(batch, channel) affine the consumer GEMM applies:
 //   y = x*scale + shift,  scale = rstd*gamma*(1+ts),  shift = (beta - mean*rstd*gamma)*(1+ts) + tb
 // where ts/tb are the resnet's timestep scale/shift (resnet.py:627-629) or absent.
@@ -138,11 +140,12 @@ __global__ __launch_bounds__(256) void k_gn_partial(const float* __restrict__ a0
       const float* src = (c < c0) ? a0 : a1;
       const int ld = (c < c0) ? c0 : c1;
       const int cc = (c < c0) ? c : c - c0;
-      float s = 0.f, q = 0.f;
+      double s = 0.0, q = 0.0;
       for (int t = t0 + rl; t < t1; t += nrl) {
         const float4 v = *reinterpret_cast<const float4*>(src + ((size_t)b * T + t) * ld + cc);
-        s += (v.x + v.y) + (v.z + v.w);
-        q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        const double x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;   // (the squares of floats are exact in fp64)
+        s += (x0 + x1) + (x2 + x3);
+        q += (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
       }
       gs[sl] = s;
       gq[sl] = q;

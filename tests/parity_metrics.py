@@ -279,23 +279,25 @@ def prompt_oracle_probes(sd, prompt, lengths, n_layers, num_heads=8):
 FF_TAIL_BOUND = 1e-4        # whole tensor and every frame: test_conv3's bound for the same split-bf16 contraction
 
 
-def ff_tail_fp64(sd, p, h3, x, drop_ff=False, swap_geglu=False):
+def ff_tail_fp64(sd, p, h3, x, drop_ff=False, swap_geglu=False, emulate=False, fault=None):
     """What k_chain_ff / k_ff_split compute for the Transformer2DModel with prefix `p` ("....attentions.0."), restated in fp64 from
     the UNMERGED state-dict weights:  proj_out(h3 + ff.net.2(GEGLU(ff.net.0(LN3(h3))))) + x,  h3 = the block after its cross
     attention, x = the transformer's input, both channels-last [B, T, C].  `drop_ff` / `swap_geglu` plant a fault (the
-    feed-forward term left out; the value and gate halves of GEGLU exchanged) for the tests that show the bound has teeth."""
+    feed-forward term left out; the value and gate halves of GEGLU exchanged) for the tests that show the bound has teeth;
+    `emulate` / `fault` are ln_linear's (below)."""
     import torch.nn.functional as F
     tb = p + "transformer_blocks.0."
     W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
     h3, x = torch.as_tensor(h3).to(torch.float64), torch.as_tensor(x).to(torch.float64)
     C = h3.shape[-1]
-    n = F.layer_norm(h3, (C,), W(tb + "norm3.weight"), W(tb + "norm3.bias"), 1e-5)
-    a, gate = F.linear(n, W(tb + "ff.net.0.proj.weight"), W(tb + "ff.net.0.proj.bias")).chunk(2, dim=-1)
+    hg = ln_linear(h3, W(tb + "norm3.weight"), W(tb + "norm3.bias"), W(tb + "ff.net.0.proj.weight"), W(tb + "ff.net.0.proj.bias"),
+                   emulate, fault)
+    a, gate = hg.chunk(2, dim=-1)
     if swap_geglu:
         a, gate = gate, a
-    ff = F.linear(a * F.gelu(gate), W(tb + "ff.net.2.weight"), W(tb + "ff.net.2.bias"))
+    ff = _linear(a * F.gelu(gate), W(tb + "ff.net.2.weight"), W(tb + "ff.net.2.bias"), emulate)
     h4 = h3 if drop_ff else h3 + ff
-    return F.linear(h4, W(p + "proj_out.weight")[:, :, 0], W(p + "proj_out.bias")) + x
+    return _linear(h4, W(p + "proj_out.weight")[:, :, 0], W(p + "proj_out.bias"), emulate) + x
 
 
 def seam_figures(per_frame, rows):
@@ -306,3 +308,172 @@ def seam_figures(per_frame, rows):
     inner = sorted(set(range(T)) - set(seams) - {0, T - 1})
     return {"first": float(per_frame[:, 0].max()), "last": float(per_frame[:, T - 1].max()),
             "seams": float(per_frame[:, seams].max()) if seams else 0.0, "inner": float(per_frame[:, inner].max()) if inner else 0.0}
+
+
+# ---- the folded-normalisation launches in isolation (tests/test_gpu_offdist.py, tests/test_offdist_reference.py) ----------------
+# Each restatement below computes one stretch of the schedule between two taps in fp64 from the UNMERGED state-dict weights.  With
+# emulate=True it does the arithmetic the kernels are documented to do instead (csrc/kernels_qkv.hip, kernels_chain.hip,
+# kernels_ffsplit.hip, gnx_device.h): every contraction operand held as two bf16 planes (hi = bf16(v), lo = bf16(v - hi)), the
+# products summed exactly (fp64 here); a LayerNorm folded into its consumer - gamma and beta in the packed weights, the RAW row in
+# the planes, mean and rstd (from the fp32 row) applied afterwards as  rstd (x W' - mean u) + b' ; a GroupNorm as one affine
+# a x + b per (utterance, channel), applied before the planes are stored; the attention logits in fp32, exp(s - max) rounded to
+# ONE fp16 plane before P V (tests/test_gpu_ops.py test_attention_frag).  The emulation is what sets the per-frame bound of the
+# GPU test (isolated_bound): it carries the cancellation of  x W' - mean u  at a large row mean that a fixed bound would have to
+# guess.  `fault` plants what a kernel could get wrong only in this regime (FAULTS).
+FAULTS = ("lost_lo", "mean_from_bf16", "beta_sign", "tscale", "skip_stats")
+
+
+def _planes(v, lo=True):
+    """What two bf16 planes hold of the fp32 tensor v, as fp64 (lo=False: the hi plane alone)."""
+    v32 = torch.as_tensor(v).to(torch.float32)
+    hi = v32.to(torch.bfloat16).float()
+    if not lo:
+        return hi.double()
+    return hi.double() + (v32 - hi).to(torch.bfloat16).double()
+
+
+def _linear(x, W, b, emulate):
+    import torch.nn.functional as F
+    return F.linear(_planes(x), _planes(W), b) if emulate else F.linear(x, W, b)
+
+
+def ln_linear(x, gamma, beta, W, b, emulate=False, fault=None, eps=1e-5):
+    """linear(LayerNorm(x) gamma + beta; W, b) in fp64, or (emulate / fault) in the folded form described above.  Faults:
+    "lost_lo" - the raw row enters the contraction as its hi plane alone; "mean_from_bf16" - the row mean is taken from the
+    bf16-rounded row, not from the fp32 row; "beta_sign" - beta folded into b' with the wrong sign."""
+    import torch.nn.functional as F
+    x = torch.as_tensor(x).double()
+    if not emulate and fault not in ("lost_lo", "mean_from_bf16", "beta_sign"):
+        return F.linear(F.layer_norm(x, (x.shape[-1],), gamma, beta, eps), W, b)
+    x32 = x.float().double()
+    mean = x32.mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((x32 - mean) ** 2).mean(-1, keepdim=True) + eps)
+    if fault == "mean_from_bf16":
+        mean = _planes(x, lo=False).mean(-1, keepdim=True)
+    Wf = _planes(W * gamma[None, :])
+    bf = (-1.0 if fault == "beta_sign" else 1.0) * (W @ beta) + (0.0 if b is None else b)
+    return rstd * (_planes(x, lo=fault != "lost_lo") @ Wf.t() - mean * Wf.sum(-1)) + bf
+
+
+def _sdpa(q, k, v, heads, bias, emulate):
+    import math
+    B, Tq, C = q.shape
+    d = C // heads
+    q, k, v = (a.reshape(B, -1, heads, d).transpose(1, 2) for a in (q, k, v))
+    s = q @ k.transpose(-1, -2) / math.sqrt(d)
+    if emulate:
+        s = s.float() if bias is None else s.float() + bias.float()[:, None]
+        s = s.double()
+    elif bias is not None:
+        s = s + bias[:, None]
+    pr = torch.exp(s - s.amax(-1, keepdim=True))
+    o = ((pr.half().double() if emulate else pr) @ v) / pr.sum(-1, keepdim=True)
+    return o.transpose(1, 2).reshape(B, Tq, C)
+
+
+def attn_chain_fp64(sd, tb, which, x, heads, enc=None, mask=None, emulate=False, fault=None):
+    """`which` = "attn1": norm1 -> self attention -> to_out + x (x = the tapped proj_in, result = the tapped attn1);
+    "attn2": norm2 -> cross attention over enc [B, L, D] under the boolean mask [B, L] -> to_out + x (attn1 -> attn2).
+    tb = "....transformer_blocks.0."."""
+    import torch.nn.functional as F
+    W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
+    x = torch.as_tensor(x).double()
+    g, b, a = W(tb + "norm%s.weight" % which[-1]), W(tb + "norm%s.bias" % which[-1]), tb + which + "."
+    q = ln_linear(x, g, b, W(a + "to_q.weight"), None, emulate, fault)
+    if enc is None:
+        k, v, bias = ln_linear(x, g, b, W(a + "to_k.weight"), None, emulate, fault), ln_linear(x, g, b, W(a + "to_v.weight"), None, emulate, fault), None
+    else:
+        e = torch.as_tensor(enc).double()
+        k, v = _linear(e, W(a + "to_k.weight"), None, emulate), _linear(e, W(a + "to_v.weight"), None, emulate)
+        bias = None if mask is None else ((1.0 - torch.as_tensor(mask).double()) * -10000.0)[:, None, :]
+    o = _sdpa(q, k, v, heads, bias, emulate)
+    return _linear(o, W(a + "to_out.0.weight"), W(a + "to_out.0.bias"), emulate) + x
+
+
+def _group_affine(x, groups, gamma, beta, eps, stats_from=None):
+    """GroupNorm of channels-last x [B, T, C] as the per-(utterance, channel) affine (a, b): y = a x + b.  stats_from: a [C] index
+    array - channel c takes the statistics of the group of channel stats_from[c] (a planted fault)."""
+    B, T, C = x.shape
+    xg = x.reshape(B, T, groups, C // groups)
+    mean = xg.mean((1, 3))
+    rstd = 1.0 / torch.sqrt(((xg - mean[:, None, :, None]) ** 2).mean((1, 3)) + eps)
+    idx = torch.arange(C) if stats_from is None else torch.as_tensor(stats_from)
+    grp = idx // (C // groups)
+    a = rstd[:, grp] * gamma[None, :]
+    return a[:, None, :], (beta[None, :] - mean[:, grp] * a)[:, None, :]
+
+
+def _conv(h, W, b, emulate):
+    import torch.nn.functional as F
+    if emulate:
+        h, W = _planes(h), _planes(W)
+    return F.conv1d(h.permute(0, 2, 1), W, b, padding=W.shape[-1] // 2).permute(0, 2, 1)
+
+
+def proj_in_fp64(sd, p, x, groups, emulate=False):
+    """The first stretch of the block head: GroupNorm (eps 1e-6) -> proj_in, x = the transformer's input (the tapped resnet block),
+    result = the tapped proj_in.  p = "....attentions.i."."""
+    W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
+    x = torch.as_tensor(x).double()
+    a, b = _group_affine(x, groups, W(p + "norm.weight"), W(p + "norm.bias"), 1e-6)
+    return _conv(a * x + b, W(p + "proj_in.weight"), W(p + "proj_in.bias"), emulate)
+
+
+def resnet_fp64(sd, p, x, emb, groups, skip=None, eps=1e-5, emulate=False, fault=None):
+    """A ResnetBlock2D from its input tap to its output tap: norm1 + SiLU -> conv1 -> norm2 (1 + scale) + shift + SiLU -> conv2 +
+    shortcut.  x [B, T, C] channels-last, emb [B, 1, E] or [B, E] (the tapped `emb`), skip: the second half of an up-path block's
+    concatenated input.  Faults: "tscale" - 1 + scale replaced by scale; "skip_stats" - the skip half's channels take the group
+    statistics of the h half's channels at the same offset (the concatenated GroupNorm indexed without the skip's channel base)."""
+    import torch.nn.functional as F
+    W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
+    x = torch.as_tensor(x).double()
+    C1 = x.shape[-1]
+    if skip is not None:
+        x = torch.cat([x, torch.as_tensor(skip).double()], -1)
+    C = x.shape[-1]
+    stats_from = None
+    if fault == "skip_stats":
+        assert skip is not None
+        stats_from = torch.cat([torch.arange(C1), torch.arange(C - C1)])
+    a, b = _group_affine(x, groups, W(p + "norm1.weight"), W(p + "norm1.bias"), eps, stats_from)
+    h = _conv(F.silu(a * x + b), W(p + "conv1.weight"), W(p + "conv1.bias"), emulate)
+    t = F.linear(F.silu(torch.as_tensor(emb).double().reshape(x.shape[0], -1)), W(p + "time_emb_proj.weight"), W(p + "time_emb_proj.bias"))
+    scale, shift = t.chunk(2, -1)
+    a, b = _group_affine(h, groups, W(p + "norm2.weight"), W(p + "norm2.bias"), eps)
+    m = (scale if fault == "tscale" else 1.0 + scale)[:, None, :]
+    h = _conv(F.silu((a * m) * h + (b * m + shift[:, None, :])), W(p + "conv2.weight"), W(p + "conv2.bias"), emulate)
+    if (p + "conv_shortcut.weight") in sd:
+        x = _conv(x, W(p + "conv_shortcut.weight"), W(p + "conv_shortcut.bias"), emulate)
+    return x + h
+
+
+def isolated_bound(emulated, want):
+    """Bound for one launch (or one stretch between taps) in isolation, whole tensor and every frame: FF_TAIL_BOUND, or - where the
+    inputs make the documented arithmetic itself cost more - 2 x the worst frame of its host emulation + 2^-16 (the factor 2 and
+    the 2^-16 as tests/test_gpu_ops.py test_attention_frag argues them)."""
+    return max(FF_TAIL_BOUND, 2.0 * frame_errors(emulated, want)["worst"] + 2.0 ** -16)
+
+
+def resnet_input_taps(n_levels=4, layers=2):
+    """{resnet block name: (tap of its input, tap of the concatenated skip or None)} for the layout of oracle.unet_ref.unet_forward:
+    down = (CrossAttn x (n - 1), Down), mid, up = (Up, CrossAttn x (n - 1))."""
+    out, skips, h = {}, ["conv_in"], "conv_in"
+    for i in range(n_levels):
+        for j in range(layers):
+            out["down_blocks.%d.resnets.%d" % (i, j)] = (h, None)
+            h = "down_blocks.%d.%s.%d" % (i, "attentions" if i < n_levels - 1 else "resnets", j)
+            skips.append(h)
+        if i < n_levels - 1:
+            h = "down_blocks.%d.downsamplers.0" % i
+            skips.append(h)
+    out["mid_block.resnets.0"] = (h, None)
+    out["mid_block.resnets.1"] = ("mid_block.attentions.0", None)
+    h = "mid_block.resnets.1"
+    for i in range(n_levels):
+        for j in range(layers + 1):
+            out["up_blocks.%d.resnets.%d" % (i, j)] = (h, skips.pop())
+            h = "up_blocks.%d.%s.%d" % (i, "attentions" if i > 0 else "resnets", j)
+        if i < n_levels - 1:
+            h = "up_blocks.%d.upsamplers.0" % i
+    assert not skips
+    return out

@@ -144,6 +144,63 @@ def test_linear_planes_geglu_any_pitch(M, K, No, ldo):
         assert np.array_equal(outs[No][0], outs[ldo][0]) and np.array_equal(outs[No][1], outs[ldo][1])
 
 
+def test_linear_planes_geglu_gate_ramp():
+    """test_linear_planes_geglu_any_pitch with the gate pre-activations spread over [-12, 12] through a bias ramp (gelu_erf's whole
+    measured range; every other test feeds it |y| of a few units): the same 3e-5."""
+    L = _lib()
+    M, K, No = 96, 64, 96
+    x, w, b = _synth("x", (M, K)), _synth("w", (2 * No, K), 1 / np.sqrt(K)), _synth("b", (2 * No,), 0.1)
+    b[No:] += np.linspace(-12.0, 12.0, No, dtype=np.float32)
+    dx, dw, db = _dev(x), _dev(w), _dev(b)
+    z = torch.from_numpy(x).double() @ torch.from_numpy(w).double().t() + torch.from_numpy(b).double()
+    assert float(z[:, No:].min()) < -11 and float(z[:, No:].max()) > 11
+    ref = (z[:, :No] * F.gelu(z[:, No:])).numpy()
+    hi = torch.full((M, No), 0x7fc1, dtype=torch.int32, device="cuda").to(torch.int16)
+    lo = hi.clone()
+    L.check(L.lib().dv_op_linear_planes(L.ptr(dx), L.ptr(dw), L.ptr(db), None, L.ptr(hi), L.ptr(lo), M, K, 2 * No, No, 1, 0, None),
+            "dv_op_linear_planes(geglu)")
+    torch.cuda.synchronize()
+    val = (hi.cpu().view(torch.bfloat16).double() + lo.cpu().view(torch.bfloat16).double()).numpy()
+    err = rel_l2(val, ref)
+    print("geglu gate ramp: %.3e" % err)
+    assert err < 3e-5, err
+
+
+@pytest.mark.parametrize("edge", ["offset30", "offset300", "constant-group", "outlier"])
+def test_group_stats_value_edges(edge):
+    """Group statistics where the data is not zero-mean unit-variance: every value offset by 30 / 300 sigma; one group constant
+    (var = 0: rstd = eps^-1/2); one group with a single 1e4 outlier.  Mean: within 2 fp32 ulp of the fp64 mean (the absolute 1e-5
+    of test_group_stats cannot hold at 300).  rstd: 1e-5 relative, every group.  (At 300 sigma rstd was 8.9e-4 off while
+    k_gn_partial summed x^2 in fp32.)"""
+    L = _lib()
+    B, T, C, G = 2, 300, 96, 8
+    x = _synth("x", (B, T, C))
+    if edge.startswith("offset"):
+        x = x + np.float32(edge[6:])
+    else:
+        x = x + np.float32(0.7)
+        if edge == "constant-group":
+            x[1, :, 3 * (C // G):4 * (C // G)] = np.float32(1.5)
+        else:
+            x[0, 137, 5 * (C // G) + 7] = np.float32(1.0e4)
+    mean = torch.empty((B, G), device="cuda")
+    rstd = torch.empty((B, G), device="cuda")
+    dx = _dev(x)
+    L.check(L.lib().dv_op_group_stats(L.ptr(dx), L.ptr(mean), L.ptr(rstd), B, T, C, G, 1e-5, None), "dv_op_group_stats")
+    torch.cuda.synchronize()
+    xg = x.astype(np.float64).reshape(B, T, G, C // G)
+    m, v = xg.mean(axis=(1, 3)), xg.var(axis=(1, 3))
+    ulp = np.spacing(np.abs(m).astype(np.float32)).astype(np.float64)
+    want = 1 / np.sqrt(v + 1e-5)
+    em = np.abs(mean.cpu().numpy() - m) / ulp
+    er = np.abs(rstd.cpu().numpy() - want) / want
+    print("group_stats %s: mean off by %.2f ulp at most, rstd %.2e relative" % (edge, em.max(), er.max()))
+    if edge == "constant-group":
+        assert v[1, 3] == 0.0 and abs(want[1, 3] - 1e5 ** 0.5) < 1e-9
+    assert em.max() <= 2.0, em
+    assert er.max() < 1e-5, er
+
+
 @pytest.mark.parametrize("B,T,C,G", [(2, 40, 32, 8), (8, 1024, 128, 8), (2, 100, 896, 8), (3, 7, 1024, 8), (2, 300, 96, 8)])
 def test_group_stats(B, T, C, G):
     L = _lib()
@@ -309,6 +366,17 @@ CONV3_SHAPES = [
 
 @pytest.mark.parametrize("B,Cin,T,Tp,Cout,Csc,up2", CONV3_SHAPES)
 def test_conv3(B, Cin, T, Tp, Cout, Csc, up2):
+    _conv3_case(B, Cin, T, Tp, Cout, Csc, up2)
+
+
+@pytest.mark.parametrize("B,Cin,T,Tp,Cout,Csc,up2", [(2, 128, 100, 128, 128, 0, 0), (2, 128, 100, 128, 128, 256, 0)], ids=["plain", "folded-shortcut"])
+def test_conv3_offset_channels_and_unit_bias(B, Cin, T, Tp, Cout, Csc, up2):
+    """test_conv3 with a quarter of the input channels (of x and of the shortcut's input) offset by + 20 sigma and an O(1) bias:
+    the same 1e-4 per tensor and per frame."""
+    _conv3_case(B, Cin, T, Tp, Cout, Csc, up2, offset=20.0, bias_scale=1.0)
+
+
+def _conv3_case(B, Cin, T, Tp, Cout, Csc, up2, offset=0.0, bias_scale=0.1):
     """The three-tap convolution through the fragment-major weights - the route of the forward to k_conv3<128 | 256 | 384 | 512>,
     k_conv3s (wider inputs, or the folded 1x1 shortcut as a second K segment; also as a fused split-K pair) and k_conv3u (nearest
     x2 upsampling) - against fp64 conv1d on the frames that exist.  The padding rows [T, Tp) of the inputs hold large finite
@@ -320,12 +388,13 @@ def test_conv3(B, Cin, T, Tp, Cout, Csc, up2):
     def padded(name, C):
         a = np.empty((B, Tp, C), dtype=np.float32)
         a[:, :T] = _synth(name, (B, T, C))
+        a[:, :T, ::4] += np.float32(offset)
         a[:, T:] = (3.0e4 * rng.standard_normal((B, Tp - T, C))).astype(np.float32)
         return a
 
     x = padded("x", Cin)
     w = _synth("w", (Cout, Cin, 3), 1.0 / np.sqrt(Cin * 3))
-    b = _synth("b", (Cout,), 0.1)
+    b = _synth("b", (Cout,), bias_scale)
     xt = torch.from_numpy(x[:, :T]).double().permute(0, 2, 1)
     if up2:
         xt = F.interpolate(xt, scale_factor=2, mode="nearest")
