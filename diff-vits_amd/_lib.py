@@ -107,6 +107,9 @@ SIGNATURES = {
     "dv_op_cfg_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p]),
     "dv_op_cfg_pair_in": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "dv_plan_graph_nodes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "dv_plan_set_known_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "dv_plan_known_coefs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "dv_op_known_frames": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_void_p]),
     "dv_op_conv1d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p]),
     "dv_op_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
     "dv_op_linear_planes": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 6 + [C.c_void_p]),

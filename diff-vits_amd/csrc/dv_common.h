@@ -467,6 +467,11 @@ hipError_t launch_dyn_thresh(float* x, int rows, int64_t n, float ratio, float m
 // 4-byte aligned addresses): out[0 .. n) = out[n .. 2 n) = in;  out[i] = fmaf(g, pair[n + i] - pair[i], pair[i]).  One launch each.
 hipError_t launch_cfg_pair_in(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_cfg_combine(const float* pair, float* out, int64_t n, float g, hipStream_t st);
+// known-frame correction of the sampler state (kernels_known.hip): x[b, :, f] = coef2[0] * known[b, :, f] + coef2[1] * eps[b, :, f] where
+// keep[b, f] != 0 (three float32 roundings), other frames are not written.  x / known / eps [rows, C, T], keep [rows, T] bytes,
+// coef2: two floats on the device.  rows * C * T < 2^31.  One launch.
+hipError_t launch_known_frames(float* x, const float* known, const float* eps, const uint8_t* keep, int rows, int C, int T,
+                               const float* coef2, hipStream_t st);
 // length regulator of the VITS prior (kernels_regulate.hip): durations -> inclusive integer prefix sums cum [B, Tx] and frame counts
 // y_len [B] (-1: an utterance with a duration outside [0, 2^24] or a total beyond int32), then the aligned prior sample
 // z_p [B, C, Tp] = m_p[.., tok(t)] + (noise * expf(logs_p[.., tok(t)])) * noise_scale, tok(t) = first j < x_len with cum[j] > t (frames

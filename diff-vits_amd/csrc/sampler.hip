@@ -127,6 +127,7 @@ struct Event {
   int dst;           // EVAL: history slot;  COMB: 0 = x, 1 = x_pred, 2 + s = history slot s (in place: x0 -> noise, DV_SOLVER_DPM)
   int coef;          // COMB: row of the coefficient table
   int slots[4];      // COMB: history slots of the m terms (-1 = unused)
+  int kf;            // row of the known-frame table whose correction of x follows this event (-1: none); mark_known_points
 };
 
 // solve A x = b (n <= MAXO), Gaussian elimination with partial pivoting (torch.linalg.solve / inv of the reference)
@@ -189,6 +190,12 @@ struct dv_plan {
   bool cfg_on = false; double cfg_scale = 1.0;
   float* cfg_in = nullptr; float* cfg_out = nullptr; int64_t cfg_numel = 0;      // 2 * numel floats each
   float* cfg_cond = nullptr; int64_t cfg_cond_numel = 0;                        // 2 * the condition's floats
+  // known-frame correction of x (dv_plan_set_known_frames): x <- alpha_t known + sigma_t eps in the kept frames, after the
+  // events mark_known_points marked.  kf_tab: (alpha, sigma) per correction point, fp64 from the plan's schedule
+  std::vector<std::array<double, 2>> kf_tab;
+  float* d_kf = nullptr;
+  const float* kf_known = nullptr; const float* kf_eps = nullptr; const uint8_t* kf_keep = nullptr;
+  int kf_rows = 0, kf_C = 0, kf_T = 0;
   // graph cache
   hipGraphExec_t exec = nullptr; hipStream_t cap_stream = nullptr;
   int64_t graph_nodes = 0;            // nodes of the captured graph (dv_plan_graph_nodes); 0 while there is none
@@ -590,6 +597,39 @@ static int build_plan(dv_plan* p) {
   return DV_OK;
 }
 
+// The points at which the reference calls correcting_xt_fn, as Plan.run_python (sampler/_plan.py) walks them: the start point
+// of a multistep method once the first evaluation is complete - behind its x0 -> noise conversion, which still reads the
+// uncorrected x - and x after every COMB that lands in x, at the grid point it lands on (the final denoise_to_zero update: t_0,
+// the last one).  The singlestep methods do not correct their start point (dpm_solver.py:1221-1232).
+static void mark_known_points(dv_plan* p) {
+  const Schedule& ns = p->ns;
+  const int n_ts = (int)p->timesteps.size();
+  auto add_row = [&](int k) {
+    const double t = p->timesteps[std::min(k, n_ts - 1)];
+    p->kf_tab.push_back({ns.alpha(t), ns.sigma(t)});
+    return (int)p->kf_tab.size() - 1;
+  };
+  p->kf_tab.clear();
+  const bool single = p->method != 0;
+  bool seen_eval = false, start_pending = false;
+  int step = 0;
+  for (size_t i = 0; i < p->ev.size(); ++i) {
+    Event& e = p->ev[i];
+    e.kf = -1;
+    if (start_pending && !(e.type == 1 && e.dst >= 2)) {
+      if (!single) p->ev[i - 1].kf = add_row(0);
+      start_pending = false;
+    }
+    if (e.type == 0) {
+      if (!seen_eval) start_pending = true;
+      seen_eval = true;
+    } else if (e.dst == 0) {
+      e.kf = add_row(++step);
+    }
+  }
+  if (start_pending && !single) p->ev.back().kf = add_row(0);
+}
+
 extern "C" int dv_sampler_plan(int32_t solver, const float* betas, int32_t n_betas, int32_t steps, int32_t order,
                                int32_t skip_type, int32_t lower_order_final, dv_plan** out) {
   return dv_sampler_plan_ex(solver, betas, n_betas, steps, order, skip_type, lower_order_final, -1.0, -1.0, 0, out);
@@ -635,6 +675,7 @@ extern "C" int dv_sampler_plan_method(int32_t solver, int32_t schedule, const fl
   else p->ns.init_continuous(schedule, beta_0, beta_1);
   int rc = build_plan(p);
   if (rc != DV_OK) { delete p; return rc; }
+  mark_known_points(p);
   *out = p;
   return DV_OK;
 }
@@ -655,6 +696,7 @@ extern "C" void dv_plan_destroy(dv_plan* p) {
   if (p->xp) (void)hipFree(p->xp);
   for (float* b : p->m) (void)hipFree(b);
   if (p->thr_ws) (void)hipFree(p->thr_ws);
+  if (p->d_kf) (void)hipFree(p->d_kf);
   for (float* b : {p->cfg_in, p->cfg_out, p->cfg_cond}) if (b) (void)hipFree(b);
   delete p;
 }
@@ -718,6 +760,31 @@ extern "C" int dv_plan_set_thresholding(dv_plan* p, double ratio, double max_val
   return DV_OK;
 }
 
+extern "C" int dv_plan_set_known_frames(dv_plan* p, const float* known, const float* eps, const uint8_t* keep,
+                                        int32_t rows, int32_t channels, int32_t frames) {
+  if (!p) return dv_fail(DV_ERR_INVALID, "dv_plan_set_known_frames: null plan");
+  if (!known) {                          // off
+    if (p->kf_known) plan_drop_graph(p);
+    p->kf_known = nullptr; p->kf_eps = nullptr; p->kf_keep = nullptr; p->kf_rows = p->kf_C = p->kf_T = 0;
+    return DV_OK;
+  }
+  if (!eps || !keep || rows < 1 || channels < 1 || frames < 1 || (int64_t)rows * channels * frames > (int64_t)INT32_MAX ||
+      (((uintptr_t)known | (uintptr_t)eps) & 3u))
+    return dv_fail(DV_ERR_INVALID, "dv_plan_set_known_frames: bad argument (known, eps, keep device pointers, the floats 4-byte "
+                                   "aligned; rows, channels, frames >= 1 with rows * channels * frames < 2^31)");
+  if (!(p->kf_known == known && p->kf_eps == eps && p->kf_keep == keep && p->kf_rows == rows && p->kf_C == channels && p->kf_T == frames))
+    plan_drop_graph(p);
+  p->kf_known = known; p->kf_eps = eps; p->kf_keep = keep; p->kf_rows = rows; p->kf_C = channels; p->kf_T = frames;
+  return DV_OK;
+}
+
+extern "C" int dv_plan_known_coefs(const dv_plan* p, int32_t* n_rows, float* rows2) {
+  if (!p) return dv_fail(DV_ERR_INVALID, "dv_plan_known_coefs: null plan");
+  if (n_rows) *n_rows = (int32_t)p->kf_tab.size();
+  if (rows2) for (size_t i = 0; i < p->kf_tab.size(); ++i) { rows2[2 * i] = (float)p->kf_tab[i][0]; rows2[2 * i + 1] = (float)p->kf_tab[i][1]; }
+  return DV_OK;
+}
+
 // nodes of the captured graph of the last dv_sampler_run (0: none - never run, dropped, or DVITS_NO_GRAPH)
 extern "C" int dv_plan_graph_nodes(const dv_plan* p, int64_t* n_nodes) {
   if (!p || !n_nodes) return dv_fail(DV_ERR_INVALID, "dv_plan_graph_nodes: null argument");
@@ -759,6 +826,12 @@ static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows, int64_t cond
     HIPCHK(hipMalloc((void**)&p->thr_ws, dyn_thresh_ws_bytes(rows)));
     p->thr_rows = rows;
   }
+  if (p->kf_known && !p->d_kf && !p->kf_tab.empty()) {
+    std::vector<float> h(p->kf_tab.size() * 2);
+    for (size_t i = 0; i < p->kf_tab.size(); ++i) { h[2 * i] = (float)p->kf_tab[i][0]; h[2 * i + 1] = (float)p->kf_tab[i][1]; }
+    HIPCHK(hipMalloc((void**)&p->d_kf, h.size() * sizeof(float)));
+    HIPCHK(hipMemcpy(p->d_kf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
   if (!p->d_coefs) {
     HIPCHK(hipMalloc((void**)&p->d_coefs, p->coefs.size() * 8 * sizeof(float)));
     HIPCHK(hipMemcpy(p->d_coefs, p->coefs.data(), p->coefs.size() * 8 * sizeof(float), hipMemcpyHostToDevice));
@@ -794,7 +867,7 @@ static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows, int64_t cond
 
 template <typename EvalFn>
 static int run_events(dv_plan* p, float* x, int64_t numel, int rows, EvalFn eval, hipStream_t st) {
-  const bool thr = p->thr_ratio >= 0.0;
+  const bool thr = p->thr_ratio >= 0.0, kf = p->kf_known != nullptr;
   for (const Event& e : p->ev) {
     if (e.type == 0) {
       int rc = eval(e.src == 0 ? x : p->xp, e.eval_idx, p->m[e.dst]);
@@ -812,6 +885,11 @@ static int run_events(dv_plan* p, float* x, int64_t numel, int rows, EvalFn eval
       hipError_t he = launch_lincomb(dst, e.src == 0 ? x : p->xp, ms[0], ms[1], ms[2], ms[3], p->d_coefs + (size_t)e.coef * 8,
                                      numel, st);
       if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "lincomb launch failed: %s", hipGetErrorString(he));
+    }
+    // correcting_xt_fn = known frames (dpm_solver.py:1180-1238, uni_pc.py:615-666; Plan.run_python: xt_hook): always on x
+    if (kf && e.kf >= 0) {
+      hipError_t he = launch_known_frames(x, p->kf_known, p->kf_eps, p->kf_keep, p->kf_rows, p->kf_C, p->kf_T, p->d_kf + (size_t)e.kf * 2, st);
+      if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "known-frame correction launch failed: %s", hipGetErrorString(he));
     }
   }
   return DV_OK;
@@ -832,6 +910,9 @@ extern "C" int dv_sampler_run(dv_plan* p, dv_unet* u, float* x_inout, const floa
   const int Bn = B;                   // rows of the network's batch
   if (cfg) B /= 2;                    // rows of x
   if (cin <= cout) cond = nullptr;    // (no channel-concat condition: the pointer is ignored, as dv_unet_enqueue ignores it)
+  if (p->kf_known && (p->kf_rows != B || p->kf_C != cout || p->kf_T != T))
+    return dv_fail(DV_ERR_INVALID, "dv_sampler_run: the plan's known frames are [%d, %d, %d], x_inout is [%d, %d, %d]",
+                   p->kf_rows, p->kf_C, p->kf_T, B, cout, T);
   const int64_t numel = (int64_t)B * cout * T, cond_numel = cond ? (int64_t)B * (cin - cout) * T : 0;
   int rc = plan_buffers(p, numel, Bn, B, cond_numel);
   if (rc != DV_OK) return rc;
@@ -901,6 +982,9 @@ static int run_custom(dv_plan* p, dv_model_fn fn, void* user, float* x_inout, in
   if (p->cfg_on)                      // (the callback evaluates one batch: it has no unconditional / conditional pair)
     return dv_fail(DV_ERR_INVALID, "%s: the plan has classifier-free guidance, which runs in dv_sampler_run only (the model callback "
                                    "has no pair of conditions) - switch it off with dv_plan_set_guidance(p, 1.0, 0)", who);
+  if (p->kf_known && (p->kf_rows != rows || (int64_t)p->kf_rows * p->kf_C * p->kf_T != numel))
+    return dv_fail(DV_ERR_INVALID, "%s: the plan's known frames are [%d, %d, %d], x_inout holds %d rows and %lld floats", who,
+                   p->kf_rows, p->kf_C, p->kf_T, rows, (long long)numel);
   int rc = plan_buffers(p, numel, 0, rows);
   if (rc != DV_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -915,6 +999,9 @@ extern "C" int dv_sampler_run_custom(dv_plan* p, dv_model_fn fn, void* user, flo
   if (!p || !fn || !x_inout || numel <= 0) return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: bad argument");
   if (p->thr_ratio >= 0.0)
     return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: the plan thresholds per row and this form has no row count - use "
+                                   "dv_sampler_run_custom_rows");
+  if (p->kf_known)
+    return dv_fail(DV_ERR_INVALID, "dv_sampler_run_custom: the plan corrects known frames per row and this form has no row count - use "
                                    "dv_sampler_run_custom_rows");
   return run_custom(p, fn, user, x_inout, 0, numel, stream, "dv_sampler_run_custom");
 }
@@ -962,5 +1049,24 @@ extern "C" int dv_op_cfg_pair_in(const float* in, float* out, int64_t numel, voi
   hipError_t he = launch_cfg_pair_in(in, out, numel, st);
   if (he == hipSuccess) he = hipStreamSynchronize(st);
   if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_cfg_pair_in failed: %s", hipGetErrorString(he));
+  return DV_OK;
+}
+
+extern "C" int dv_op_known_frames(float* x_inout, const float* known, const float* eps, const uint8_t* keep,
+                                  int32_t rows, int32_t channels, int32_t frames, double alpha, double sigma, void* stream) {
+  if (!x_inout || !known || !eps || !keep || rows < 1 || channels < 1 || frames < 1 ||
+      (int64_t)rows * channels * frames > (int64_t)INT32_MAX || (((uintptr_t)x_inout | (uintptr_t)known | (uintptr_t)eps) & 3u))
+    return dv_fail(DV_ERR_INVALID, "dv_op_known_frames: bad argument (rows, channels, frames >= 1, rows * channels * frames < 2^31, "
+                                   "4-byte aligned float pointers)");
+  if (!std::isfinite(alpha) || !std::isfinite(sigma)) return dv_fail(DV_ERR_INVALID, "dv_op_known_frames: alpha %g / sigma %g must be finite", alpha, sigma);
+  hipStream_t st = (hipStream_t)stream;
+  float* coef = nullptr;
+  HIPCHK(hipMalloc((void**)&coef, 2 * sizeof(float)));
+  const float h[2] = {(float)alpha, (float)sigma};
+  hipError_t he = hipMemcpy(coef, h, sizeof(h), hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = launch_known_frames(x_inout, known, eps, keep, rows, channels, frames, coef, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  (void)hipFree(coef);
+  if (he != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_known_frames failed: %s", hipGetErrorString(he));
   return DV_OK;
 }

@@ -363,7 +363,8 @@ class NaturalSpeech2(nn.Module):
 
     @torch.no_grad()
     def sample_from_prior(self, content, refer=None, text_lengths=None, spec_lengths=None, vocos=None, sample_method="unipc", noise=None,
-                          guidance_scale=1.0, negative_refer=None, negative_lengths=None, voices=None):
+                          guidance_scale=1.0, negative_refer=None, negative_lengths=None, voices=None,
+                          known_mel=None, known_mask=None, known_noise=None, paste_known=True):
         """(content, refer) -> (audio | None, mel): reference model3.py:1162-1203 after the `vits.infer` call.
         guidance_scale != 1: classifier-free guidance (model_wrapper(guidance_type='classifier-free'), dpm_solver.py:322-330)
         between the speaker prompt and `negative_refer` [B, 100, L'] with `negative_lengths` (None: all-zero encoder states
@@ -371,7 +372,14 @@ class NaturalSpeech2(nn.Module):
         generic path.  With the defaults nothing changes.
         voices: one enrolled `Voice` per batch row (`enroll_voice`) in place of `refer` / `spec_lengths`, which may then be
         None: the prompt encoder and the denoiser's conditioning pass are skipped - the HIP engine binds the voices' records to
-        the rows (`UNetEngine.bind_voices`), the torch backend takes their encoder states.  Not together with guidance."""
+        the rows (`UNetEngine.bind_voices`), the torch backend takes their encoder states.  Not together with guidance.
+        known_mel [B, dim, T'] (the sampler's own domain: what this method returns as `mel`) with known_mask, a bool [B, T']:
+        the frames under the mask are held on the forward process of known_mel while the others are generated (editing,
+        infilling, continuing a recording) - a `KnownFrames` correction, inside the one hipGraph on the HIP backend and as the
+        solver's correcting_xt_fn on the torch backend; together with guidance and with voices.  known_noise [B, dim, T']: the
+        noise of that forward process (None: the run's own start noise x_T - the kept region of the start point is then
+        consistent with the rest of it).  paste_known: write known_mel back into the kept frames of the returned mel (without
+        it they hold alpha_0 known + sigma_0 noise at the last grid point).  With known_mel=None nothing changes."""
         if sample_method not in ("unipc", "dpmsolver"):
             raise ValueError("sample_method %r is not supported (this build: 'unipc', 'dpmsolver')" % (sample_method,))
         guided = float(guidance_scale) != 1.0
@@ -394,6 +402,11 @@ class NaturalSpeech2(nn.Module):
         audio = torch.randn(shape, device=dev) if noise is None else noise.to(dev)
         if tuple(audio.shape) != shape:
             raise ValueError("noise must have shape %s, got %s" % (shape, tuple(audio.shape)))
+        if (known_mel is None) != (known_mask is None):
+            raise ValueError("known_mel and known_mask go together")
+        if known_mel is not None and (tuple(known_mel.shape) != shape or tuple(known_mask.shape) != (shape[0], shape[2])):
+            raise ValueError("known_mel must be %s and known_mask %s, got %s and %s"
+                             % (shape, (shape[0], shape[2]), tuple(known_mel.shape), tuple(known_mask.shape)))
         data = (content, refer, text_lengths, spec_lengths)
         native = self.diff_model.backend == "hip" and audio.is_cuda
         if sample_method == "unipc":
@@ -457,6 +470,13 @@ class NaturalSpeech2(nn.Module):
             model_fn = model_wrapper(self.sample_fun, noise_schedule, model_type="x_start", model_kwargs={"data": data})
             solver = (UniPC(model_fn, noise_schedule, variant="bh2") if sample_method == "unipc"
                       else DPM_Solver(model_fn, noise_schedule, algorithm_type="dpmsolver++"))
+        known = None
+        if known_mel is not None:
+            from .sampler._plan import KnownFrames
+            known = KnownFrames(solver.noise_schedule, known_mel.to(dev, torch.float32), known_mask.to(dev),
+                                audio if known_noise is None else known_noise.to(dev, torch.float32))
+        solver.correcting_xt_fn = known          # (the native solvers are kept across calls: set or cleared every time)
+
         def run():
             if sample_method == "unipc":
                 return solver.sample(audio, steps=30, order=2, skip_type="time_uniform", method="multistep")
@@ -478,6 +498,8 @@ class NaturalSpeech2(nn.Module):
                     raise RuntimeError("in-kernel hand-over timed out on the fallback schedule (it has none): internal error")
         else:
             mel = run()
+        if known is not None and paste_known:
+            mel = torch.where(known.keep, known.known.to(mel.dtype), mel)
         if vocos is None:
             return None, mel
         vocos.to(mel.device)
@@ -489,11 +511,12 @@ class NaturalSpeech2(nn.Module):
     @torch.no_grad()
     def sample(self, text, spec, text_lengths, spec_lengths, tone, language, vocos, sampling_timesteps=200,
                sample_method="unipc", noise=None, prior_noise=None, guidance_scale=1.0, negative_refer=None, negative_lengths=None,
-               voices=None):
+               voices=None, known_mel=None, known_mask=None, known_noise=None, paste_known=True):
         """reference model3.py:1119-1203 (same positional signature).  `noise` = x_T, `prior_noise` = the prior's
         normal draw (forwarded as `noise=` to this package's VITS.infer); both default to fresh torch.randn draws.
         guidance_scale / negative_refer / negative_lengths: classifier-free guidance, see sample_from_prior.
-        voices: enrolled voices for the diffusion side (sample_from_prior); the prior still reads `spec` / `spec_lengths`."""
+        voices: enrolled voices for the diffusion side (sample_from_prior); the prior still reads `spec` / `spec_lengths`.
+        known_mel / known_mask / known_noise / paste_known: known-frame correction (infilling), see sample_from_prior."""
         self.sampling_timesteps = sampling_timesteps
         if not hasattr(self, "vits"):
             raise RuntimeError("NaturalSpeech2.sample needs the VITS prior: construct with vits=<module with .infer(...)> "
@@ -503,7 +526,8 @@ class NaturalSpeech2(nn.Module):
         else:
             content, refer = self.vits.infer(text, text_lengths, spec, spec_lengths, tone, language, noise=prior_noise)
         return self.sample_from_prior(content, refer, text_lengths, spec_lengths, vocos, sample_method, noise,
-                                      guidance_scale, negative_refer, negative_lengths, voices=voices)
+                                      guidance_scale, negative_refer, negative_lengths, voices=voices, known_mel=known_mel,
+                                      known_mask=known_mask, known_noise=known_noise, paste_known=paste_known)
 
 
 # ---- SURVEY.md §8f rank 3 (inference side of the VITS prior, from the text encoder's outputs onward) ------------------

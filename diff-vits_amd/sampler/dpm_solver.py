@@ -11,10 +11,10 @@ methods 'multistep' (reference :1171-1213, :547-592, :796-904), 'singlestep' and
 import torch
 
 from ._adaptive import adaptive_sample
-from ._plan import (NativeUNetModel, NoiseScheduleBase, Plan, _eval_times, dynamic_thresholding, native_graph_model, sample_with_plan,
-                    wrap_model)
+from ._plan import (KnownFrames, NativeUNetModel, NoiseScheduleBase, Plan, _eval_times, dynamic_thresholding, native_graph_model,
+                    sample_with_plan, wrap_model)
 
-__all__ = ["NoiseScheduleVP", "model_wrapper", "DPM_Solver", "NativeUNetModel"]
+__all__ = ["NoiseScheduleVP", "model_wrapper", "DPM_Solver", "NativeUNetModel", "KnownFrames"]
 
 _SOLVER_DPMPP = 0
 _SOLVER_DPM = 4          # algorithm_type='dpmsolver': multistep updates on the noise prediction (include/dvits_hip.h)
@@ -37,7 +37,8 @@ class DPM_Solver:
         # correcting_x0_fn ("dynamic_thresholding" or fn(x0, t)) / correcting_xt_fn (fn(x, t, step)): reference :409-415.  With
         # a callable the loop is stepped from Python (the hooks are arbitrary), never replayed as one graph.  Dynamic
         # thresholding is a closed form: it is compiled into the native plan (dv_plan_set_thresholding) whenever the run
-        # would otherwise be a graph replay - sample() decides; stepped runs apply it with torch.
+        # would otherwise be a graph replay - sample() decides; stepped runs apply it with torch.  A `KnownFrames` as
+        # correcting_xt_fn is a closed form too (dv_plan_set_known_frames), under the same rule.
         self._thresholding = None
         if correcting_x0_fn == "dynamic_thresholding":
             self._thresholding = (float(dynamic_thresholding_ratio), float(thresholding_max_val))
@@ -54,17 +55,20 @@ class DPM_Solver:
         return torch.as_tensor(plan.timesteps, dtype=torch.float32, device=device)
 
     def _plan(self, steps, order, skip_type, lower_order_final, t_start=None, t_end=None, denoise_to_zero=False,
-              solver_type="dpmsolver", method="multistep", thresholding=None):
+              solver_type="dpmsolver", method="multistep", thresholding=None, known_frames=False):
         key = (steps, order, skip_type, bool(lower_order_final), t_start, t_end, bool(denoise_to_zero), solver_type, method)
         if thresholding is not None:       # (a thresholded graph and a plain one never share a handle)
             key += (thresholding,)
+        if known_frames:                   # (nor a corrected one)
+            key += ("known_frames",)
         if key not in self._plans:
             solver = _SOLVER_DPMPP if self.algorithm_type == "dpmsolver++" else _SOLVER_DPM
             if solver_type == "taylor":
                 solver = _TAYLOR[solver]
             self._plans[key] = Plan(solver, self.noise_schedule._betas, steps, order, skip_type,
                                     lower_order_final, t_start, t_end, denoise_to_zero,
-                                    schedule=self.noise_schedule._plan_schedule(), method=method, thresholding=thresholding)
+                                    schedule=self.noise_schedule._plan_schedule(), method=method, thresholding=thresholding,
+                                    known_frames=known_frames)
         return self._plans[key]
 
     def sample(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep",
@@ -98,15 +102,21 @@ class DPM_Solver:
             raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
         assert steps >= order
         plan = self._plan(steps, order, skip_type, lower_order_final, t_start, t_end, denoise_to_zero, solver_type, method)
-        if (self._thresholding is not None and self.correcting_xt_fn is None and not return_intermediate
-                and native_graph_model(self.model_fn, x) is not None):
-            # dynamic thresholding inside the graph: the mask is the rule of x0_hook below
-            only_last = self.algorithm_type != "dpmsolver++"
-            mask = tuple((not only_last) or (bool(denoise_to_zero) and e == plan.nfe - 1) for e in range(plan.nfe))
-            if any(mask):
+        kf = self.correcting_xt_fn if isinstance(self.correcting_xt_fn, KnownFrames) else None
+        closed_x0 = self.correcting_x0_fn is None or self._thresholding is not None
+        if ((self._thresholding is not None or kf is not None) and closed_x0 and (self.correcting_xt_fn is None or kf is not None)
+                and not return_intermediate and native_graph_model(self.model_fn, x) is not None):
+            # dynamic thresholding inside the graph: the mask is the rule of x0_hook below; known frames inside the graph
+            thr = None
+            if self._thresholding is not None:
+                only_last = self.algorithm_type != "dpmsolver++"
+                mask = tuple((not only_last) or (bool(denoise_to_zero) and e == plan.nfe - 1) for e in range(plan.nfe))
+                if any(mask):
+                    thr = self._thresholding + (mask,)
+            if thr is not None or kf is not None:
                 plan = self._plan(steps, order, skip_type, lower_order_final, t_start, t_end, denoise_to_zero, solver_type, method,
-                                  thresholding=self._thresholding + (mask,))
-            return sample_with_plan(plan, self.model_fn, self.noise_schedule, x)
+                                  thresholding=thr, known_frames=kf is not None)
+            return sample_with_plan(plan, self.model_fn, self.noise_schedule, x, known_frames=kf)
         x0_hook = None
         if self.correcting_x0_fn is not None:
             # data_prediction_fn applies it (:433-445): every evaluation of 'dpmsolver++'; with 'dpmsolver' only the final

@@ -85,7 +85,8 @@ def refer_prompt(refer, device):
 def synthesize(model, cfg, vocos, batchs, control_values=None, device="cuda", prompt_length="reference", **sample_kw):
     """tts_infer.py:46-75 with the same batch tuples `(phoneme, tone, language, refer, phoneme_length)`; returns the last
     batch's samples like the reference (and its mel as a second value).  `control_values` is accepted and, as in the
-    reference, unused.  Extra keywords (`sample_method`, `noise`, `prior_noise`) go to `model.sample`.
+    reference, unused.  Extra keywords (`sample_method`, `noise`, `prior_noise`, `known_mel` / `known_mask` / `known_noise` /
+    `paste_known` for infilling, ...) go to `model.sample`.
 
     prompt_length: tts_infer.py:68 passes `refer.size(1)` - the mel CHANNEL count, 100 - as the prompt length, so the
     prompt masks cover the first 100 frames whatever the audio's length.  "reference" keeps that; "frames" passes the

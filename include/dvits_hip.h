@@ -344,6 +344,28 @@ int dv_plan_set_guidance(dv_plan* p, double scale, int32_t on);
  * change, DVITS_NO_GRAPH=1).  For measurements and tests: what a captured loop really holds. */
 int dv_plan_graph_nodes(const dv_plan* p, int64_t* n_nodes);
 
+/* Known-frame correction (mel infilling: keep a set of frames on the forward process of a known signal while the rest is
+ * generated) as part of the compiled loop - the closed form of a correcting_xt_fn (dpm_solver.py:384-394; uni_pc.py:256-261):
+ *     x[b, :, f] <- alpha_t * known[b, :, f] + sigma_t * eps[b, :, f]   where keep[b, f] != 0,   unchanged elsewhere,
+ * at exactly the points where the reference calls correcting_xt_fn (dpm_solver.py:1180-1238, uni_pc.py:615-666).  Multistep
+ * methods: the start point once the first evaluation is complete (an x0 -> noise conversion of that evaluation still reads the
+ * uncorrected x), then x after every update that lands in x (UniPC: after the corrector), the denoise_to_zero result
+ * included.  Singlestep methods: after every outer step; the start point is not corrected.  t is the grid point the step
+ * lands on; (alpha, sigma) come from the plan's own schedule in fp64 and are applied as floats - fadd(fmul(alpha, known),
+ * fmul(sigma, eps)), the three float32 roundings of the torch expression.
+ * known / eps [rows, channels, frames] float32 and keep [rows, frames] uint8 are DEVICE pointers that stay valid and keep
+ * their addresses across runs (their contents may change between runs: a captured graph reads them on replay).
+ * known == NULL switches the correction off.  Any change of a pointer or of the shape drops the captured graph; setting the
+ * same values again is free.  dv_sampler_run refuses (DV_ERR_INVALID, before anything is launched) a plan whose rows /
+ * channels / frames are not those of x_inout - under guidance x_inout holds B rows and the correction sees those B rows;
+ * dv_sampler_run_custom_rows takes rows from its argument and needs rows * channels * frames == numel; dv_sampler_run_custom
+ * has no row count and refuses such a plan.  Cost: one elementwise launch per correction point. */
+int dv_plan_set_known_frames(dv_plan* p, const float* known, const float* eps, const uint8_t* keep,
+                             int32_t rows, int32_t channels, int32_t frames);
+/* The correction points of the plan, with or without dv_plan_set_known_frames: *n_rows of them, rows2 [n_rows][2] =
+ * (alpha, sigma) as the floats the loop applies, in the order of the launches.  Either output may be NULL. */
+int dv_plan_known_coefs(const dv_plan* p, int32_t* n_rows, float* rows2);
+
 /* ---- prompt encoder: PromptEncoder.forward, reference model3.py:408-433 ------------------
  * The reference recomputes it inside every denoiser call (Diffusion_Encoder.forward, model3.py:902-906) although it
  * does not depend on the step; the host mirror calls this once per sampler run and feeds the result to
@@ -476,6 +498,12 @@ int dv_op_cfg_combine(const float* x0_pair, float* out, int32_t rows, int64_t ro
 /* The other guidance kernel (k_cfg_pair_in): out[0 .. numel) = out[numel .. 2 numel) = in[0 .. numel), no overlap, any
  * 4-byte aligned addresses, 1 <= numel <= 2^40; DV_ERR_INVALID before anything is launched otherwise. */
 int dv_op_cfg_pair_in(const float* in, float* out, int64_t numel, void* stream);
+/* The known-frame correction on the kernel the sampler loop runs (k_known_frames): x_inout / known / eps [rows, channels,
+ * frames] float32, keep [rows, frames] uint8 (device);  x <- float(alpha) * known + float(sigma) * eps in the kept frames (three
+ * float32 roundings), the others are not written.  rows * channels * frames < 2^31, 4-byte aligned float pointers (16-byte
+ * aligned ones and frames % 4 == 0 take the vector route); DV_ERR_INVALID before anything is launched otherwise. */
+int dv_op_known_frames(float* x_inout, const float* known, const float* eps, const uint8_t* keep,
+                       int32_t rows, int32_t channels, int32_t frames, double alpha, double sigma, void* stream);
 
 #ifdef __cplusplus
 }
