@@ -77,6 +77,10 @@ SIGNATURES = {
     "dv_op_rel_attention": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_regulate_lengths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_op_regulate_sample": (C.c_int, [C.c_void_p] * 5 + [C.c_double] + [C.c_int32] * 4 + [C.c_void_p] * 4),
+    "dv_op_mas_scores": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 2),
+    "dv_op_mas_scratch_bytes": (C.c_int64, [C.c_int32] * 3),
+    "dv_op_mas_path": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "dv_op_mas_path_timed": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p]),
     "dv_unet_time_family": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_int32)]),
     "dv_unet_persist_ticks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]),

@@ -511,9 +511,11 @@ class NaturalSpeech2(nn.Module):
     @torch.no_grad()
     def sample(self, text, spec, text_lengths, spec_lengths, tone, language, vocos, sampling_timesteps=200,
                sample_method="unipc", noise=None, prior_noise=None, guidance_scale=1.0, negative_refer=None, negative_lengths=None,
-               voices=None, known_mel=None, known_mask=None, known_noise=None, paste_known=True):
+               voices=None, known_mel=None, known_mask=None, known_noise=None, paste_known=True, durations=None):
         """reference model3.py:1119-1203 (same positional signature).  `noise` = x_T, `prior_noise` = the prior's
         normal draw (forwarded as `noise=` to this package's VITS.infer); both default to fresh torch.randn draws.
+        durations: integer [B, Tx], pinned frame counts for the prior (forwarded to this package's VITS.infer; -1 keeps a
+        token's prediction).
         guidance_scale / negative_refer / negative_lengths: classifier-free guidance, see sample_from_prior.
         voices: enrolled voices for the diffusion side (sample_from_prior); the prior still reads `spec` / `spec_lengths`.
         known_mel / known_mask / known_noise / paste_known: known-frame correction (infilling), see sample_from_prior."""
@@ -521,10 +523,10 @@ class NaturalSpeech2(nn.Module):
         if not hasattr(self, "vits"):
             raise RuntimeError("NaturalSpeech2.sample needs the VITS prior: construct with vits=<module with .infer(...)> "
                                "or call sample_from_prior(content, refer, ...)")
-        if prior_noise is None:
-            content, refer = self.vits.infer(text, text_lengths, spec, spec_lengths, tone, language)
-        else:
-            content, refer = self.vits.infer(text, text_lengths, spec, spec_lengths, tone, language, noise=prior_noise)
+        prior_kw = {} if prior_noise is None else {"noise": prior_noise}
+        if durations is not None:
+            prior_kw["durations"] = durations
+        content, refer = self.vits.infer(text, text_lengths, spec, spec_lengths, tone, language, **prior_kw)
         return self.sample_from_prior(content, refer, text_lengths, spec_lengths, vocos, sample_method, noise,
                                       guidance_scale, negative_refer, negative_lengths, voices=voices, known_mel=known_mel,
                                       known_mask=known_mask, known_noise=known_noise, paste_known=paste_known)
@@ -743,6 +745,153 @@ class TextEncoder(nn.Module):
         return x, m, logs, x_mask
 
 
+class WN(nn.Module):
+    """reference modules.WN (modules.py:133-210): a stack of gated dilated convolutions with skip connections, conditioned on
+    g [B, gin, 1] through one 1x1 convolution whose output is cut into the layers' slices.  The convolutions carry weight norm
+    under the reference's parameter names (`weight_g` / `weight_v`)."""
+
+    def __init__(self, hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=0, p_dropout=0):
+        super().__init__()
+        if kernel_size % 2 != 1:
+            raise ValueError("kernel_size must be odd, got %d" % kernel_size)
+        wn = torch.nn.utils.weight_norm
+        self.hidden_channels, self.n_layers, self.gin_channels = hidden_channels, n_layers, gin_channels
+        self.in_layers, self.res_skip_layers = nn.ModuleList(), nn.ModuleList()
+        if gin_channels != 0:
+            self.cond_layer = wn(nn.Conv1d(gin_channels, 2 * hidden_channels * n_layers, 1), name="weight")
+        for i in range(n_layers):
+            dilation = dilation_rate ** i
+            self.in_layers.append(wn(nn.Conv1d(hidden_channels, 2 * hidden_channels, kernel_size, dilation=dilation,
+                                               padding=(kernel_size - 1) * dilation // 2), name="weight"))
+            out = 2 * hidden_channels if i < n_layers - 1 else hidden_channels         # the last layer has no residual half
+            self.res_skip_layers.append(wn(nn.Conv1d(hidden_channels, out, 1), name="weight"))
+
+    def forward(self, x, x_mask, g=None):
+        H = self.hidden_channels
+        skip = torch.zeros_like(x)
+        if g is not None:
+            g = self.cond_layer(g)
+        for i, (gate, mix) in enumerate(zip(self.in_layers, self.res_skip_layers)):
+            h = gate(x)
+            if g is not None:
+                h = h + g[:, 2 * H * i:2 * H * (i + 1)]
+            h = mix(torch.tanh(h[:, :H]) * torch.sigmoid(h[:, H:]))
+            if i < self.n_layers - 1:
+                x = (x + h[:, :H]) * x_mask
+                skip = skip + h[:, H:]
+            else:
+                skip = skip + h
+        return skip * x_mask
+
+
+class PosteriorEncoder(nn.Module):
+    """reference model3.PosteriorEncoder (model3.py:526-572): mel frames -> the posterior's statistics and one draw from it,
+    (z, m, logs, mask).  `noise=` [B, out_channels, T] fixes the draw (None: torch.randn_like, as the reference).  Sixteen
+    WaveNet layers of torch ops on the tensor's device: the forced aligner's only user runs it once per recording."""
+
+    def __init__(self, in_channels, out_channels, hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=0):
+        super().__init__()
+        self.out_channels = out_channels
+        self.pre = nn.Conv1d(in_channels, hidden_channels, 1)
+        self.enc = WN(hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=gin_channels)
+        self.proj = nn.Conv1d(hidden_channels, out_channels * 2, 1)
+
+    def forward(self, x, x_lengths, g=None, noise=None):
+        x_mask = torch.unsqueeze(sequence_mask(x_lengths, x.size(2)), 1).to(x.dtype)
+        h = self.enc(self.pre(x) * x_mask, x_mask, g=g)
+        m, logs = torch.split(self.proj(h) * x_mask, self.out_channels, dim=1)
+        eps = torch.randn_like(m) if noise is None else noise.to(m)
+        return (m + eps * torch.exp(logs)) * x_mask, m, logs, x_mask
+
+
+MAS_NEG = -1e9          # the search's "impossible" score (exact in float32)
+MAS_MAX_TX = 512        # the native search's limit on the padded token count (the text encoder's own)
+
+
+def mas_scores(z, m_p, logs_p):
+    """Alignment scores [B, Ty, Tx] of frames z [B, C, Ty] under the tokens' diagonal normals (m_p, logs_p [B, C, Tx]): the log
+    density summed over the channels, as two matmuls and two per-token sums (reference model3.py:767-780)."""
+    s = torch.exp(-2 * logs_p)
+    per_token = (-0.5 * math.log(2 * math.pi) - logs_p).sum(1) + (-0.5 * m_p * m_p * s).sum(1)      # [B, Tx]
+    zt = z.transpose(1, 2)
+    return per_token.unsqueeze(1) + torch.matmul(-0.5 * zt * zt, s) + torch.matmul(zt, m_p * s)
+
+
+def mas_search(neg_cent, y_lengths, x_lengths):
+    """Monotonic alignment search on the host, one row of the table at a time with the columns vectorised, in float32 (one
+    addition per cell: the integers are those of the reference's routine).  neg_cent [B, Ty, Tx] -> (durations int64 [B, Tx],
+    frame_token int64 [B, Ty]); zeros / -1 behind an utterance's lengths.  An utterance with t_x < 1, t_y < 1, t_x > t_y or a
+    length beyond the padded dimensions is not searched: both its rows are all -1.  The input is not modified."""
+    B, Ty, Tx = neg_cent.shape
+    v_all = neg_cent.detach().to("cpu", torch.float32)
+    durations = torch.zeros((B, Tx), dtype=torch.int64)
+    frame_token = torch.full((B, Ty), -1, dtype=torch.int64)
+    neg = torch.tensor(MAS_NEG, dtype=torch.float32)
+    for b, (ty, tx) in enumerate(zip(y_lengths.tolist(), x_lengths.tolist())):
+        if tx < 1 or ty < 1 or tx > ty or tx > Tx or ty > Ty:
+            durations[b] = -1
+            continue
+        v = v_all[b, :ty, :tx]
+        cols = torch.arange(tx)
+        q = torch.zeros(tx, dtype=torch.float32)
+        step = torch.zeros((ty, tx), dtype=torch.bool)       # would the walk leave token x after frame y?
+        for y in range(ty):
+            left = torch.cat([neg.reshape(1) if y else torch.zeros(1), q[:-1]])
+            on_diagonal = cols == y
+            step[y] = (cols != 0) & (on_diagonal | (q < left))
+            q = v[y] + torch.maximum(left, torch.where(on_diagonal, neg, q))
+        token = tx - 1
+        for y in range(ty - 1, -1, -1):
+            frame_token[b, y] = token
+            token -= int(step[y, token])
+        durations[b, :tx] = torch.bincount(frame_token[b, :ty], minlength=tx)
+    return durations, frame_token
+
+
+def edit_known_frames(mel, old_durations, new_durations, old_span, new_span):
+    """The known frames of an edit.  mel [B, dim, T_old] (the sampler's domain) is laid out by the resolved integer durations
+    old_durations [B, Tx_old]; the edit replaces the tokens old_span[b] = (first, end) by the tokens new_span[b] of the new text,
+    whose resolved durations are new_durations [B, Tx_new].  Returns (known_mel [B, dim, T_new], known_mask bool [B, T_new]),
+    T_new = the longest new utterance: the frames of the tokens before the span are copied to the same tokens' frames, those of
+    the tokens behind it move by the change in length, the frames of new_span (and the padding) are unmasked zeros.  An unchanged
+    token whose duration differs between the two tensors is a ValueError.  Integer indexing only."""
+    old_d, new_d = (torch.as_tensor(d).to("cpu", torch.int64) for d in (old_durations, new_durations))
+    old_s, new_s = (torch.as_tensor(s).to("cpu", torch.int64).reshape(-1, 2) for s in (old_span, new_span))
+    B, T_old = mel.shape[0], mel.shape[2]
+    if old_d.dim() != 2 or new_d.dim() != 2 or not (old_d.shape[0] == new_d.shape[0] == old_s.shape[0] == new_s.shape[0] == B):
+        raise ValueError("durations must be [B, Tx] and spans [B, 2] for the %d utterances of mel" % B)
+    if bool((old_d < 0).any()) or bool((new_d < 0).any()):
+        raise ValueError("durations must be resolved (>= 0): pass what infer(return_durations=True) / align returned")
+    pre, old_mid, new_mid, post = ([0] * B for _ in range(4))
+    for b in range(B):
+        (o0, o1), (n0, n1) = old_s[b].tolist(), new_s[b].tolist()
+        if not (0 <= o0 <= o1 <= old_d.shape[1] and 0 <= n0 <= n1 <= new_d.shape[1]) or o0 != n0:
+            raise ValueError("utterance %d: spans %s -> %s must be half-open token ranges that start at the same token"
+                             % (b, (o0, o1), (n0, n1)))
+        tail_o, tail_n = old_d[b, o1:], new_d[b, n1:]
+        n = max(len(tail_o), len(tail_n))
+        tail_o, tail_n = F.pad(tail_o, (0, n - len(tail_o))), F.pad(tail_n, (0, n - len(tail_n)))
+        for what, a, c, off in (("before", old_d[b, :o0], new_d[b, :n0], 0), ("behind", tail_o, tail_n, o1)):
+            diff = torch.nonzero(a != c)
+            if len(diff):
+                j = int(diff[0])
+                raise ValueError("utterance %d: unchanged token %d (%s the span) lasts %d frames in old_durations and %d in "
+                                 "new_durations" % (b, off + j, what, int(a[j]), int(c[j])))
+        pre[b], old_mid[b], new_mid[b], post[b] = (int(old_d[b, :o0].sum()), int(old_d[b, o0:o1].sum()),
+                                                   int(new_d[b, n0:n1].sum()), int(tail_o.sum()))
+        if pre[b] + old_mid[b] + post[b] > T_old:
+            raise ValueError("utterance %d: old_durations cover %d frames, mel has %d" % (b, pre[b] + old_mid[b] + post[b], T_old))
+    T_new = max(max(p + n + q for p, n, q in zip(pre, new_mid, post)), 1)
+    dev = mel.device
+    pre, old_mid, new_mid, post = (torch.tensor(v, dtype=torch.int64, device=dev).unsqueeze(1) for v in (pre, old_mid, new_mid, post))
+    t = torch.arange(T_new, dtype=torch.int64, device=dev).unsqueeze(0)
+    head = t < pre
+    known_mask = head | ((t >= pre + new_mid) & (t < pre + new_mid + post))
+    src = torch.where(head, t, t - new_mid + old_mid).clamp_(0, max(T_old - 1, 0))
+    known_mel = torch.gather(mel, 2, src.unsqueeze(1).expand(B, mel.shape[1], T_new)) * known_mask.unsqueeze(1).to(mel.dtype)
+    return known_mel, known_mask
+
+
 class VITS(nn.Module):
     """Inference side of the reference's prior (model3.py:646-860): `infer` = reference encoder (TextTimeEmbedding, one
     head) -> text encoder -> DurationPredictor_unet -> monotonic alignment -> prior sample -> 6-layer `o_proj`
@@ -754,18 +903,28 @@ class VITS(nn.Module):
     predictor's UNet and `o_proj` run on the HIP engine (backend='hip'); the once-per-utterance glue (reference encoder,
     alignment path, gathers) is a handful of torch ops on the same device, or with prior_backend='hip' (opt-in) the native
     length regulator (dv_op_regulate_*, csrc/kernels_regulate.hip: GPU tensors only, never a fall-back).  `noise=` fixes the
-    prior noise (the reference draws torch.randn_like)."""
+    prior noise (the reference draws torch.randn_like).
+
+    `durations=` (infer, infer_from_encoder) pins frame counts: an integer [B, Tx] tensor whose entries >= 0 replace
+    ceil(exp(logw) * length_scale) of their tokens and whose entries of -1 keep the prediction; `return_durations=True` appends
+    the resolved integer durations to the return value.  With aligner=True the posterior encoder `enc_q` (reference names) is
+    built and `align` gives the frames of a recording to the tokens of its transcript (the reference's training-time monotonic
+    alignment search, model3.py:755-798): torch ops and a host search by default, align_backend='hip' for the two native
+    operators dv_op_mas_scores / dv_op_mas_path (csrc/kernels_align.hip; GPU tensors only, never a fall-back)."""
 
     def __init__(self, n_vocab=None, spec_channels=None, inter_channels=128, hidden_channels=256, filter_channels=256,
                  n_heads=2, n_layers=6, kernel_size=3, p_dropout=0.1, gin_channels=256, enc_p=None, n_tones=11, n_languages=3,
-                 backend=None, text_encoder_backend=None, prior_backend=None, **unused):
+                 backend=None, text_encoder_backend=None, prior_backend=None, aligner=False, **unused):
         super().__init__()
         from .unet1d.embeddings import TextTimeEmbedding
         if prior_backend not in (None, "hip"):
             raise ValueError("prior_backend must be None or 'hip', got %r" % (prior_backend,))
         self.prior_backend = prior_backend     # None: the torch ops of infer_from_encoder; 'hip': dv_op_regulate_* (opt-in)
         self.native_regulator_calls = 0        # how often the native length regulator ran (tests tell the paths apart by it)
+        self.native_align_calls = 0            # how often the native aligner (scores + search) ran
         self.inter_channels, self.hidden_channels, self.gin_channels = inter_channels, hidden_channels, gin_channels
+        if aligner:
+            self.enc_q = PosteriorEncoder(100, inter_channels, hidden_channels, 5, 1, 16, gin_channels)
         if enc_p is not None:
             self.enc_p = enc_p
         elif n_vocab is not None:
@@ -778,20 +937,34 @@ class VITS(nn.Module):
 
     @torch.no_grad()
     def infer_from_encoder(self, x, m_p, logs_p, x_mask, x_lengths, y, y_lengths, g=None, noise_scale=0.667, length_scale=1,
-                           noise=None):
-        """reference model3.py:839-860 (after the `enc_p` call).  Returns (z [B, inter, T'], y, y_lengths')."""
+                           noise=None, durations=None, return_durations=False):
+        """reference model3.py:839-860 (after the `enc_p` call).  Returns (z [B, inter, T'], y, y_lengths'), and with
+        return_durations=True the resolved integer durations [B, Tx] (int64, zeros behind x_lengths) as a fourth value.
+        durations: integer [B, Tx]; >= 0 pins a token's frame count, -1 keeps the prediction."""
         if g is None:
             g = self.ref_enc(y.transpose(1, 2)).unsqueeze(-1)
         if self.prior_backend == "hip":
             for name, t in (("x", x), ("m_p", m_p), ("logs_p", logs_p), ("x_lengths", x_lengths), ("y", y)):
                 if not t.is_cuda:
                     raise RuntimeError("prior_backend='hip' needs GPU tensors; got %s on %s" % (name, t.device))
+        if durations is not None:
+            if durations.is_floating_point() or durations.is_complex() or durations.dtype == torch.bool \
+                    or tuple(durations.shape) != (m_p.shape[0], m_p.shape[2]):
+                raise ValueError("durations must be an integer tensor %s, got %s %s"
+                                 % ((m_p.shape[0], m_p.shape[2]), durations.dtype, tuple(durations.shape)))
+            durations = durations.to(device=m_p.device, dtype=torch.int64)
+            if bool((durations < -1).any()) or bool((durations > 1 << 24).any()):
+                raise ValueError("durations entries must be -1 (keep the prediction) or 0 .. 2^24 frames")
         logw = self.dp(x, x_lengths, y, y_lengths)
         if self.prior_backend == "hip":
-            z_p, y_len = self._regulate_hip(logw, m_p, logs_p, x_lengths, noise_scale, length_scale, noise)
+            z_p, y_len, resolved = self._regulate_hip(logw, m_p, logs_p, x_lengths, noise_scale, length_scale, noise, durations,
+                                                      return_durations)
         else:
             w = torch.exp(logw) * x_mask * length_scale
             w_ceil = torch.ceil(w)
+            if durations is not None:
+                w_ceil = torch.where(durations.unsqueeze(1) >= 0, durations.unsqueeze(1).to(w_ceil.dtype), w_ceil) * x_mask
+            resolved = w_ceil.squeeze(1).long() if return_durations else None
             y_len = torch.clamp_min(torch.sum(w_ceil, [1, 2]), 1).long()
             y_mask = torch.unsqueeze(sequence_mask(y_len, None), 1).to(x_mask.dtype)
             attn = generate_path(w_ceil, torch.unsqueeze(x_mask, 2) * torch.unsqueeze(y_mask, -1))
@@ -799,12 +972,16 @@ class VITS(nn.Module):
             logs_p = torch.matmul(attn.squeeze(1), logs_p.transpose(1, 2)).transpose(1, 2)
             eps = torch.randn_like(m_p) if noise is None else noise.to(m_p)
             z_p = m_p + eps * torch.exp(logs_p) * noise_scale
-        return self.o_proj(z_p, y_len, g), y, y_len
+        out = (self.o_proj(z_p, y_len, g), y, y_len)
+        return out + (resolved,) if return_durations else out
 
-    def _regulate_hip(self, logw, m_p, logs_p, x_lengths, noise_scale, length_scale, noise):
+    def _regulate_hip(self, logw, m_p, logs_p, x_lengths, noise_scale, length_scale, noise, durations=None, return_durations=False):
         """The native length regulator (csrc/kernels_regulate.hip): durations -> integer prefix sums and frame counts
         (dv_op_regulate_lengths), one read of the frame counts, the aligned prior sample (dv_op_regulate_sample).  Returns
-        (z_p [B, C, T'], y_len int64 [B]); an utterance whose durations are not finite or exceed 2^24 frames is a ValueError."""
+        (z_p [B, C, T'], y_len int64 [B], resolved durations int64 [B, Tx] or None); an utterance whose durations are not finite
+        or exceed 2^24 frames is a ValueError.  Given `durations`, the predicted counts are the differences of the kernel's
+        prefix sums, the pinned entries replace theirs, and the prefix sums of the result go to dv_op_regulate_sample; an
+        utterance whose prediction is invalid is refused only if one of its tokens keeps the prediction."""
         from . import _lib
         B, C, Tx = m_p.shape
         dev = m_p.device
@@ -816,6 +993,17 @@ class VITS(nn.Module):
         L = _lib.lib()
         _lib.check(L.dv_op_regulate_lengths(_lib.ptr(logw32), _lib.ptr(xl), B, Tx, float(length_scale), _lib.ptr(cum), _lib.ptr(y_len),
                                             _lib.stream_ptr()), "dv_op_regulate_lengths")
+        resolved = None
+        if durations is not None or return_durations:
+            inside = sequence_mask(xl, Tx)
+            cum64 = cum.to(torch.int64)
+            resolved = torch.diff(cum64, dim=1, prepend=torch.zeros((B, 1), device=dev, dtype=torch.int64)) * inside
+        if durations is not None:
+            keeps = ((durations < 0) & inside).any(1)                 # utterances that still need their prediction
+            resolved = torch.where(durations >= 0, durations, resolved) * inside
+            total = resolved.sum(1)
+            cum =torch.cumsum(resolved, 1).clamp_max(2 ** 31 - 1).to(torch.int32).contiguous()
+            y_len = torch.where(((y_len < 1) & keeps) | (total > 2 ** 31 - 1), torch.full_like(y_len, -1), torch.clamp_min(total, 1))
         counts = y_len.tolist()                # the one device-to-host read (the torch path has it in sequence_mask(y_len, None))
         bad = [b for b, n in enumerate(counts) if n < 1]
         if bad:
@@ -833,15 +1021,78 @@ class VITS(nn.Module):
         _lib.check(L.dv_op_regulate_sample(_lib.ptr(m32), _lib.ptr(logs32), _lib.ptr(cum), _lib.ptr(xl), _lib.ptr(eps), float(noise_scale),
                                            B, C, Tx, Tp, _lib.ptr(z_p), None, None, _lib.stream_ptr()), "dv_op_regulate_sample")
         self.native_regulator_calls += 1
-        return z_p.to(m_p.dtype), y_len
+        return z_p.to(m_p.dtype), y_len, resolved
 
     @torch.no_grad()
     def infer(self, x, x_lengths, y, y_lengths, tone, language, noise_scale=0.667, length_scale=1, noise_scale_w=0.8,
-              max_len=None, sdp_ratio=0, noise=None):
-        """reference model3.py:817-860 (same positional signature); returns (z, y)."""
+              max_len=None, sdp_ratio=0, noise=None, durations=None, return_durations=False):
+        """reference model3.py:817-860 (same positional signature); returns (z, y), with return_durations=True
+        (z, y, resolved durations int64 [B, Tx]).  durations: see infer_from_encoder."""
         if not hasattr(self, "enc_p"):
             raise RuntimeError("VITS.infer needs the text encoder: construct with enc_p=<module> or call infer_from_encoder")
         g = self.ref_enc(y.transpose(1, 2)).unsqueeze(-1)
         x, m_p, logs_p, x_mask = self.enc_p(x, x_lengths, tone, language, g)
-        z, y, _ = self.infer_from_encoder(x, m_p, logs_p, x_mask, x_lengths, y, y_lengths, g, noise_scale, length_scale, noise)
-        return z, y
+        out = self.infer_from_encoder(x, m_p, logs_p, x_mask, x_lengths, y, y_lengths, g, noise_scale, length_scale, noise,
+                                      durations, return_durations)
+        return (out[0], out[1], out[3]) if return_durations else (out[0], out[1])
+
+    @torch.no_grad()
+    def align(self, x, x_lengths, y, y_lengths, tone, language, noise=None, align_backend=None, return_scores=False):
+        """Forced alignment of the recording y [B, 100, Ty] (mel frames, y_lengths) against its transcript x [B, Tx] (token ids,
+        x_lengths): reference encoder -> text encoder -> posterior encoder -> alignment scores -> monotonic alignment search
+        (reference model3.py:755-794).  Returns (durations int64 [B, Tx]: frames per token, zeros behind x_lengths;
+        frame_token int64 [B, Ty]: the token of every frame, -1 behind y_lengths) on y's device; return_scores=True appends the
+        score tensor [B, Ty, Tx] the search ran on.  noise [B, inter_channels, Ty] fixes the posterior draw (None: randn).
+        align_backend=None: torch ops and the host search (mas_scores / mas_search); 'hip': dv_op_mas_scores and
+        dv_op_mas_path on the GPU, no copy of the scores to the host - a RuntimeError on CPU tensors, never a fall-back.  An
+        utterance that cannot be aligned (fewer frames than tokens, an empty side) is a ValueError naming it."""
+        if align_backend not in (None, "hip"):
+            raise ValueError("align_backend must be None or 'hip', got %r" % (align_backend,))
+        if not hasattr(self, "enc_q"):
+            raise RuntimeError("VITS.align needs the posterior encoder: construct with aligner=True")
+        if not hasattr(self, "enc_p"):
+            raise RuntimeError("VITS.align needs the text encoder: construct with n_vocab= or enc_p=<module>")
+        if align_backend == "hip":
+            for name, t in (("x", x), ("x_lengths", x_lengths), ("y", y), ("y_lengths", y_lengths), ("tone", tone), ("language", language)):
+                if not t.is_cuda:
+                    raise RuntimeError("align_backend='hip' needs GPU tensors; got %s on %s" % (name, t.device))
+        g = self.ref_enc(y.transpose(1, 2)).unsqueeze(-1)
+        _, m_p, logs_p, _ = self.enc_p(x, x_lengths, tone, language, g)
+        z, _, _, _ = self.enc_q(y, y_lengths, g, noise=noise)
+        if align_backend == "hip":
+            durations, frame_token, scores = self._align_hip(z, m_p, logs_p, y_lengths, x_lengths)
+        else:
+            scores = mas_scores(z, m_p, logs_p)
+            durations, frame_token = (t.to(y.device) for t in mas_search(scores, y_lengths, x_lengths))
+        bad = torch.nonzero(durations[:, 0] < 0).flatten().tolist()
+        if bad:
+            b = bad[0]
+            raise ValueError("utterance %d cannot be aligned: %d frames for %d tokens (both must be >= 1, and no more tokens than "
+                             "frames)" % (b, int(y_lengths[b]), int(x_lengths[b])))
+        return (durations, frame_token, scores) if return_scores else (durations, frame_token)
+
+    def _align_hip(self, z, m_p, logs_p, y_lengths, x_lengths):
+        """The native aligner (csrc/kernels_align.hip): dv_op_mas_scores, then dv_op_mas_path on its output - two launches on
+        the current stream, no wait.  Returns (durations int64 [B, Tx], frame_token int64 [B, Ty], scores float32 [B, Ty, Tx])."""
+        from . import _lib
+        B, C, Ty = z.shape
+        Tx = m_p.shape[2]
+        if Tx > MAS_MAX_TX:
+            raise ValueError("align_backend='hip' takes at most %d tokens (padded), got %d" % (MAS_MAX_TX, Tx))
+        dev = z.device
+        z32, m32, logs32 = (t.detach().to(torch.float32).contiguous() for t in (z, m_p, logs_p))
+        yl, xl = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (y_lengths, x_lengths))
+        scores = torch.empty((B, Ty, Tx), device=dev, dtype=torch.float32)
+        durations = torch.empty((B, Tx), device=dev, dtype=torch.int32)
+        frame_token = torch.empty((B, Ty), device=dev, dtype=torch.int32)
+        L = _lib.lib()
+        need = L.dv_op_mas_scratch_bytes(B, Ty, Tx)
+        if need < 0:
+            raise ValueError("align_backend='hip' cannot search B = %d, Ty = %d, Tx = %d" % (B, Ty, Tx))
+        scratch = torch.empty((need,), device=dev, dtype=torch.uint8) if need else None
+        _lib.check(L.dv_op_mas_scores(_lib.ptr(z32), _lib.ptr(m32), _lib.ptr(logs32), _lib.ptr(yl), _lib.ptr(xl), B, C, Ty, Tx,
+                                      _lib.ptr(scores), _lib.stream_ptr()), "dv_op_mas_scores")
+        _lib.check(L.dv_op_mas_path(_lib.ptr(scores), _lib.ptr(yl), _lib.ptr(xl), B, Ty, Tx, _lib.ptr(durations), _lib.ptr(frame_token),
+                                    _lib.ptr(scratch), need, _lib.stream_ptr()), "dv_op_mas_path")
+        self.native_align_calls += 1
+        return durations.long(), frame_token.long(), scores

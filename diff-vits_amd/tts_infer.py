@@ -10,6 +10,7 @@ both are outside the diffusion hot path and their third-party dependencies are a
     exactly as in the reference, and raises ImportError when it is missing.
 Training-only checkpoint entries (the posterior encoder `vits.enc_q.*`) are not
 part of the inference model and are skipped when loading; every key the inference model owns must be present.
+`aligner=True` builds the posterior encoder for `VITS.align` (forced alignment): its entries are then the model's own and load.
 """
 import torch
 
@@ -17,14 +18,16 @@ from .engine import Voice
 from .mel import reference_mel_prompt
 from .model3 import VITS, NaturalSpeech2
 
-# reference state-dict entries that only training uses: the posterior encoder (model3.py:704-712; infer never calls it)
+# reference state-dict entries that only training uses: the posterior encoder (model3.py:704-712; infer never calls it).  A model
+# built with aligner=True owns them, so they are loaded like any other entry
 TRAINING_ONLY_PREFIXES = ("vits.enc_q.",)
 
 
-def build_model(cfg, n_vocab, backend=None, text_encoder_backend=None, prior_backend=None):
-    """NaturalSpeech2(cfg) as model3.py:955-975 builds it: VITS(len(symbols), window_size // 2 + 1, **cfg['vits'])."""
+def build_model(cfg, n_vocab, backend=None, text_encoder_backend=None, prior_backend=None, aligner=False):
+    """NaturalSpeech2(cfg) as model3.py:955-975 builds it: VITS(len(symbols), window_size // 2 + 1, **cfg['vits']).
+    aligner=True: with the posterior encoder `vits.enc_q` (VITS.align), whose checkpoint entries load_state then loads."""
     vits = VITS(n_vocab, cfg["data"]["window_size"] // 2 + 1, backend=backend, text_encoder_backend=text_encoder_backend,
-                prior_backend=prior_backend, **cfg["vits"])
+                prior_backend=prior_backend, aligner=aligner, **cfg["vits"])
     return NaturalSpeech2(cfg, vits=vits, backend=backend)
 
 
@@ -42,7 +45,7 @@ def load_state(model, state_dict):
     return skipped
 
 
-def load_model(model_path, device, cfg, n_vocab=None, backend=None):
+def load_model(model_path, device, cfg, n_vocab=None, backend=None, aligner=False):
     """tts_infer.py:76-81: torch.load -> NaturalSpeech2(cfg) -> load_state_dict(data['model']) -> .to(device).eval()."""
     data = torch.load(model_path, map_location="cpu", weights_only=True)
     if not isinstance(data, dict) or "model" not in data:
@@ -52,7 +55,7 @@ def load_model(model_path, device, cfg, n_vocab=None, backend=None):
         if "vits.enc_p.emb.weight" not in sd:
             raise ValueError("checkpoint has no vits.enc_p.emb.weight; pass n_vocab")
         n_vocab = sd["vits.enc_p.emb.weight"].shape[0]
-    model = build_model(cfg, n_vocab, backend=backend)
+    model = build_model(cfg, n_vocab, backend=backend, aligner=aligner)
     load_state(model, sd)
     return model.to(device).eval()
 

@@ -444,6 +444,33 @@ int dv_op_regulate_sample(const float* m_p, const float* logs_p, const int32_t* 
                           double noise_scale, int32_t B, int32_t C, int32_t Tx, int32_t Tp, float* z_p, float* m_p_exp,
                           float* logs_p_exp, void* stream);
 
+/* Forced alignment (csrc/kernels_align.hip; reference model3.py:767-794 and monotonic_align/core.py), scores (k_mas_scores):
+ * z float32 [B, C, Ty] (the posterior sample), m_p, logs_p float32 [B, C, Tx] (the prior's statistics), y_lengths / x_lengths DEVICE
+ * int64 [B] (clamped to 0..Ty / 0..Tx) -> neg_cent float32 [B, Ty, Tx], with s = exp(-2 logs_p):
+ *   sum_c(-0.5 log 2 pi - logs_p) + sum_c(-0.5 z^2 s) + sum_c(z m_p s) + sum_c(-0.5 m_p^2 s)
+ * in plain float32, the roundings in the order the kernel's header comment lists: within (C + 6) * 2^-23 * (the sum of the
+ * summands' magnitudes) of the exact value.  Cells outside an utterance's y_lengths[b] x x_lengths[b] are written as zeros.
+ * Null pointers, a dimension < 1, B > 65535: DV_ERR_INVALID before anything is launched.  One launch, no allocation, no wait. */
+int dv_op_mas_scores(const float* z, const float* m_p, const float* logs_p, const int64_t* y_lengths, const int64_t* x_lengths,
+                     int32_t B, int32_t C, int32_t Ty, int32_t Tx, float* neg_cent, void* stream);
+/* Bytes of device scratch dv_op_mas_path needs at these sizes: 0 while the decision bits fit in LDS (Ty * ceil(Tx / 8) <= 65536:
+ * every Ty <= 1024), B * Ty * 64 beyond; -1 for sizes the search refuses (a dimension < 1, Tx > 512, Ty > 16384). */
+int64_t dv_op_mas_scratch_bytes(int32_t B, int32_t Ty, int32_t Tx);
+/* The monotonic alignment search (k_mas_path, one wave per utterance): neg_cent float32 [B, Ty, Tx] (READ ONLY - the reference
+ * accumulates in place), the two DEVICE int64 length arrays -> durations int32 [B, Tx] (frames per token, zeros behind x_lengths[b])
+ * and frame_token int32 [B, Ty] (the token of every frame, -1 behind y_lengths[b]).  The integers are exactly those of the
+ * reference's routine: one float32 addition per cell, ties stay on the token.  An utterance with x_lengths[b] < 1, y_lengths[b] < 1,
+ * x_lengths[b] > y_lengths[b] or a length beyond Tx / Ty is not searched: both its rows are all -1 and the other utterances are
+ * unaffected - a value for the caller to check, not a fault.  Scores that are not finite: unspecified path.  scratch: 16-byte aligned
+ * device memory of at least dv_op_mas_scratch_bytes(B, Ty, Tx) bytes (may be NULL when that is 0).  Null pointers, a dimension < 1,
+ * Tx > 512, Ty > 16384, too little scratch: DV_ERR_INVALID before anything is launched.  One launch, no allocation, no wait. */
+int dv_op_mas_path(const float* neg_cent, const int64_t* y_lengths, const int64_t* x_lengths, int32_t B, int32_t Ty, int32_t Tx,
+                   int32_t* durations, int32_t* frame_token, void* scratch, int64_t scratch_bytes, void* stream);
+/* The same search with two clock stamps per wave (a measuring instantiation; the one above executes none): ticks DEVICE int64 [B, 2]
+ * = (the row loop, the whole wave) in ticks of the 100 MHz constant clock; zeros for an utterance that is not searched. */
+int dv_op_mas_path_timed(const float* neg_cent, const int64_t* y_lengths, const int64_t* x_lengths, int32_t B, int32_t Ty, int32_t Tx,
+                         int32_t* durations, int32_t* frame_token, void* scratch, int64_t scratch_bytes, int64_t* ticks, void* stream);
+
 /* y[B,Cout,T_out] = conv1d(act(x)) on channels-first tensors, through the implicit-GEMM
  * kernel: k = 1 or 3, stride 1/2, padding (k-1)/2, optional nearest upsample to `up_T`
  * frames first (0 = none).  w: [Cout, Cin, k] float32, bias [Cout] or NULL. */
