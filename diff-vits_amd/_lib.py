@@ -121,7 +121,14 @@ SIGNATURES = {
     "dv_op_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_attention_frag": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_conv3": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 7 + [C.c_void_p]),
+    "dv_op_layer_norm": (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
+    "dv_op_layer_norm_into": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_float] + [C.c_int32] * 3 + [C.c_void_p]),
+    "dv_op_prompt_pre": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),
+    "dv_op_linear_ln": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 5 + [C.c_void_p] * 4),
+    "dv_op_linear_gn": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_float, C.c_int32] + [C.c_void_p] * 5),
 }
+LN_STATS, LN_ROWS, LN_APPLY, LN_AFFINE = 0, 1, 2, 3
+GN_STAT16, GN_SLAB, GN_KSTAT16 = 0, 1, 2
 
 _lib = None
 

@@ -78,7 +78,7 @@ struct GemmParams {
   bf16_t* out_hi;               // split-plane output [M, ldo] or null
   bf16_t* out_lo;
   int ldo;
-  float* stats;                 // [ceil(M/32), N, 2] per 32-row block column (sum, sumsq) or null
+  float* stats;                 // [ceil(M/32), N, 2] per 32-row block column (sum, squared deviations from the column's block mean) or null
   float* stats16;               // [M/32, N/16, 2] per (32-row, 16-column) block (sum, sumsq) or null (N % 16 == 0)
   const bf16_t* zero_page;      // DV_ZERO_PAGE_BYTES of zeros (source of padded / out-of-range rows: a lane that reads it walks
                                 // along a row's k-tiles inside it - 2 bytes per channel of the widest source tensor)
@@ -363,7 +363,7 @@ hipError_t launch_pack_input(const float* x, int cx, const float* cond, int cc, 
 // fp32 [n] -> split planes
 hipError_t launch_split(const float* in, bf16_t* hi, bf16_t* lo, int64_t n, hipStream_t st);
 // GroupNorm (+temb scale/shift) (+SiLU) of the channel concat [a0 | a1] -> split planes [B*T, c0+c1].
-// Statistics come either from the producers' per-32-row-block column sums (slab0/slab1, T % 32 == 0) or
+// Statistics come either from the producers' per-32-row-block column words (slab0/slab1: sum, M2 about the block mean; T % 32 == 0) or
 // from a precomputed per-(batch,channel) affine (scale_in/shift_in).  raw_hi/raw_lo (optional): split
 // planes of the un-normalised input (operand of the folded 1x1 shortcut).
 struct GnApplyParams {

@@ -2969,3 +2969,176 @@ extern "C" int dv_op_conv3(const float* x, const float* w, const float* bias, co
   HIPCHK(hipStreamSynchronize(st));
   return DV_OK;
 }
+
+// ----------------------------------------------------------------------------- normalisation entry points
+// The LayerNorm / GroupNorm routes of the forward through the launchers the engine calls (include/dvits_hip.h).
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int dv_op_layer_norm(const float* x, const float* gamma, const float* beta, const float* rowmask, float* y, uint16_t* y_hi,
+                                uint16_t* y_lo, float* mean, float* rstd, int32_t M, int32_t C, float eps, int32_t route, void* stream) {
+  if (!x || M <= 0 || C <= 0 || !(eps >= 0.f) || !std::isfinite(eps)) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: bad argument");
+  if (C % 4 != 0 || C > 2048) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: C = %d must be a multiple of 4, <= 2048", C);
+  if (!al16(x) || !al16(gamma) || !al16(beta) || !al16(y) || !al16(y_hi) || !al16(y_lo))
+    return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: x, gamma, beta and the outputs must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e;
+  switch (route) {
+    case DV_LN_STATS:
+      if (!mean || !rstd || y || y_hi || y_lo || rowmask) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_STATS writes mean and rstd only");
+      e = launch_ln_stats(x, mean, rstd, M, C, eps, st);
+      break;
+    case DV_LN_ROWS:
+      if (!gamma || !beta || !y || y_hi || y_lo || mean || rstd || rowmask) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_ROWS needs gamma, beta and y only");
+      e = launch_layernorm_rows(x, gamma, beta, y, M, C, eps, st);
+      break;
+    case DV_LN_APPLY:
+      if (!y_hi || y || gamma || beta || mean || rstd || rowmask) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_APPLY writes planes only, without affine");
+      e = launch_ln_apply(x, y_hi, y_lo, M, C, eps, st);
+      break;
+    case DV_LN_AFFINE:
+      if (!gamma || !beta || (!y && !y_hi) || (y_lo && !y_hi) || mean || rstd) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_AFFINE needs gamma, beta and y and / or planes");
+      e = launch_ln_affine(x, gamma, beta, rowmask, y, y_hi, y_lo, M, C, eps, st);
+      break;
+    default:
+      return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: route %d is not one of DV_LN_*", route);
+  }
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_layer_norm: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
+extern "C" int dv_op_layer_norm_into(const float* x, const float* gamma, const float* beta, float* y, int32_t M, int32_t C, float eps,
+                                     int32_t rows_per_batch, int32_t out_rows_per_batch, int32_t out_row_off, void* stream) {
+  if (!x || !gamma || !beta || !y || M <= 0 || C <= 0 || !(eps >= 0.f) || !std::isfinite(eps)) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: bad argument");
+  if (C % 4 != 0 || C > 2048) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: C = %d must be a multiple of 4, <= 2048", C);
+  if (rows_per_batch <= 0 || M % rows_per_batch != 0 || out_row_off < 0 || out_row_off > out_rows_per_batch - rows_per_batch)
+    return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: %d rows per utterance do not fit slots of %d rows at offset %d (M = %d)", rows_per_batch,
+                   out_rows_per_batch, out_row_off, M);
+  if (!al16(x) || !al16(gamma) || !al16(beta) || !al16(y)) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: pointers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_layernorm_rows_into(x, gamma, beta, y, M, C, eps, rows_per_batch, out_rows_per_batch, out_row_off, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_layer_norm_into: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
+extern "C" int dv_op_prompt_pre(const float* prompt, const float* keep, const float* gamma, const float* beta, uint16_t* hi, uint16_t* lo,
+                                float* key_bias, int32_t B, int32_t C, int32_t L, int32_t cpad, float eps, void* stream) {
+  if (!prompt || !keep || !gamma || !beta || !hi || !key_bias || B <= 0 || L <= 0 || !(eps >= 0.f) || !std::isfinite(eps))
+    return dv_fail(DV_ERR_INVALID, "dv_op_prompt_pre: bad argument");
+  if (C < 1 || C > 512 || cpad < C || cpad > 512) return dv_fail(DV_ERR_INVALID, "dv_op_prompt_pre: 1 <= C = %d <= cpad = %d <= 512 is required", C, cpad);
+  if ((int64_t)B * L > INT32_MAX / 512) return dv_fail(DV_ERR_INVALID, "dv_op_prompt_pre: B * L = %lld exceeds %d", (long long)B * L, INT32_MAX / 512);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_prompt_pre(prompt, keep, gamma, beta, hi, lo, key_bias, B, C, L, cpad, eps, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_prompt_pre: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
+// Producer GEMM (+ residual) with the raw planes and the row partials of ln_produce, then the consumer GEMM as ln_consume sets it
+// up: gamma folded into the packed weights, u and the beta-folded bias by the packing launchers Builder::pack runs.
+extern "C" int dv_op_linear_ln(const float* x, const float* w1, const float* b1, const float* res, const float* gamma, const float* beta,
+                               const float* w2, const float* b2, int32_t M, int32_t K, int32_t C, int32_t N, int32_t fused, float* y1,
+                               float* rowstat, float* y2, void* stream) {
+  if (!x || !w1 || !gamma || !beta || !w2 || !y1 || !y2 || M <= 0 || N <= 0 || (fused != 0 && fused != 1) || (fused && !rowstat))
+    return dv_fail(DV_ERR_INVALID, "dv_op_linear_ln: bad argument");
+  if (K <= 0 || K % 32 != 0 || 2 * (size_t)K + 256 > DV_ZERO_PAGE_BYTES) return dv_fail(DV_ERR_INVALID, "dv_op_linear_ln: K = %d must be a multiple of 32 within one source tensor's width", K);
+  if (C <= 0 || C % 32 != 0 || C > 512) return dv_fail(DV_ERR_INVALID, "dv_op_linear_ln: C = %d must be a multiple of 32, <= 512 (the consumer holds 16 partials per row)", C);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(gemm_init());
+  gemm_env_refresh();
+  HIPCHK(attn_init());
+  const int Cpad = rup(C, 128), Npad = rup(N, 128);
+  OpScratch sc;
+  bf16_t* xh = sc.get<bf16_t>((size_t)M * K * 2, st, false); bf16_t* xl = sc.get<bf16_t>((size_t)M * K * 2, st, false);
+  bf16_t* w1h = sc.get<bf16_t>((size_t)Cpad * K * 2, st, true); bf16_t* w1l = sc.get<bf16_t>((size_t)Cpad * K * 2, st, true);
+  bf16_t* w2h = sc.get<bf16_t>((size_t)Npad * C * 2, st, true); bf16_t* w2l = sc.get<bf16_t>((size_t)Npad * C * 2, st, true);
+  bf16_t* ph = sc.get<bf16_t>((size_t)M * C * 2, st, false); bf16_t* pl = sc.get<bf16_t>((size_t)M * C * 2, st, false);
+  float* u = sc.get<float>((size_t)Npad * 4, st, true); float* pb = sc.get<float>((size_t)Npad * 4, st, true);
+  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
+  if (!xh || !xl || !w1h || !w1l || !w2h || !w2l || !ph || !pl || !u || !pb || !zp) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: hipMalloc failed");
+  HIPCHK(launch_split(x, xh, xl, (int64_t)M * K, st));
+  PackSpec s{};
+  s.src = w1; s.N = C; s.kind = 0; s.C = K; s.taps = 1; s.c_pad = K;
+  HIPCHK(launch_pack_weight(s, w1h, w1l, K, st));
+  s.src = w2; s.N = N; s.C = C; s.c_pad = C; s.kscale = gamma;   // (both routes: k_ln_apply has no affine either)
+  HIPCHK(launch_pack_weight(s, w2h, w2l, C, st));
+  HIPCHK(launch_fold_bias(w2, nullptr, gamma, u, N, C, 0, 0, st));
+  HIPCHK(launch_fold_bias(w2, b2, beta, pb, N, C, 0, 0, st));
+  GemmParams g{};
+  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl; g.seg[0].c0 = K; g.seg[0].taps = 1;
+  g.nseg = 1; g.B = 1; g.T_in = g.T_out = g.T_virt = M; g.stride = 1;
+  g.w_hi = w1h; g.w_lo = w1l; g.Kp = K; g.N_pad = Cpad; g.bias = b1;
+  g.M = M; g.N = C; g.epi = res ? EPI_RESIDUAL : EPI_STORE; g.res = res; g.ldres = C; g.out = y1; g.ldo = C; g.zero_page = zp;
+  if (fused) { g.out_hi = ph; g.out_lo = pl; g.rowstat_out = rowstat; }
+  hipError_t e = launch_gemm(g, DV_PREC_BF16X3, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: producer launch failed: %s", hipGetErrorString(e));
+  if (!fused) {
+    e = launch_ln_apply(y1, ph, pl, M, C, 1e-5f, st);
+    if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: k_ln_apply launch failed: %s", hipGetErrorString(e));
+  }
+  GemmParams c{};
+  c.seg[0].a0_hi = ph; c.seg[0].a0_lo = pl; c.seg[0].c0 = C; c.seg[0].taps = 1;
+  c.nseg = 1; c.B = 1; c.T_in = c.T_out = c.T_virt = M; c.stride = 1;
+  c.w_hi = w2h; c.w_lo = w2l; c.Kp = C; c.N_pad = Npad; c.bias = pb;
+  c.M = M; c.N = N; c.epi = EPI_STORE; c.out = y2; c.ldo = N; c.zero_page = zp;
+  if (fused) { c.ln_stat = rowstat; c.ln_nblk = C / 32; c.ln_u = u; c.ln_eps = 1e-5f; }
+  e = launch_gemm(c, DV_PREC_BF16X3, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: consumer launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
+extern "C" int dv_op_linear_gn(const float* x, const float* w, const float* b, const float* gamma, const float* beta, int32_t B, int32_t T,
+                               int32_t Tp, int32_t K, int32_t C, int32_t G, float eps, int32_t route, float* y, float* stats,
+                               uint16_t* y_norm_hi, uint16_t* y_norm_lo, void* stream) {
+  if (!x || !w || !gamma || !beta || !y || !y_norm_hi || !y_norm_lo || B <= 0 || T <= 0 || C <= 0 || G <= 0 || !(eps >= 0.f) || !std::isfinite(eps))
+    return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: bad argument");
+  if (route != DV_GN_STAT16 && route != DV_GN_SLAB && route != DV_GN_KSTAT16) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: route %d is not one of DV_GN_*", route);
+  if (K <= 0 || K % 32 != 0 || 2 * (size_t)K + 256 > DV_ZERO_PAGE_BYTES) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: K = %d must be a multiple of 32 within one source tensor's width", K);
+  if (Tp % 32 != 0 || T > Tp || T <= Tp - 32) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: Tp = %d must be a multiple of 32 with Tp - 32 < T = %d <= Tp", Tp, T);
+  if ((int64_t)B * Tp > INT32_MAX / 2048) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: B * Tp = %lld rows are too many", (long long)B * Tp);
+  if (C % G != 0 || G > 64 || C / G > 512) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: C = %d, G = %d: at most 64 groups of at most 512 channels", C, G);
+  if (route == DV_GN_SLAB ? (C / G) % 4 != 0 : (C / G) % 16 != 0)
+    return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: %d channels per group: block statistics need whole 16-channel blocks, the column slab multiples of 4", C / G);
+  // the column slab's consumer and the standalone k_stat16 have no padded-row form (launch_gn_apply, launch_stat16)
+  if (route != DV_GN_STAT16 && T != Tp) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: this route has no padded-row form: T = %d must equal Tp = %d", T, Tp);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(gemm_init());
+  gemm_env_refresh();
+  HIPCHK(attn_init());
+  const int M = B * Tp, Npad = rup(C, 128);
+  const size_t nstat = route == DV_GN_SLAB ? (size_t)(M / 32) * C * 2 : (size_t)(M / 32) * (C / 16) * 2;
+  OpScratch sc;
+  bf16_t* xh = sc.get<bf16_t>((size_t)M * K * 2, st, false); bf16_t* xl = sc.get<bf16_t>((size_t)M * K * 2, st, false);
+  bf16_t* wh = sc.get<bf16_t>((size_t)Npad * K * 2, st, true); bf16_t* wl = sc.get<bf16_t>((size_t)Npad * K * 2, st, true);
+  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
+  float* sbuf = stats ? stats : sc.get<float>(nstat * 4, st, false);
+  if (!xh || !xl || !wh || !wl || !zp || !sbuf) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: hipMalloc failed");
+  HIPCHK(launch_split(x, xh, xl, (int64_t)M * K, st));
+  PackSpec s{};
+  s.src = w; s.N = C; s.kind = 0; s.C = K; s.taps = 1; s.c_pad = K;
+  HIPCHK(launch_pack_weight(s, wh, wl, K, st));
+  GemmParams g{};
+  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl; g.seg[0].c0 = K; g.seg[0].taps = 1;
+  g.nseg = 1; g.B = B; g.T_in = g.T_out = Tp; g.Tv_in = g.Tv_out = g.T_virt = T; g.stride = 1;
+  g.w_hi = wh; g.w_lo = wl; g.Kp = K; g.N_pad = Npad; g.bias = b;
+  g.M = M; g.N = C; g.epi = EPI_STORE; g.out = y; g.ldo = C; g.zero_page = zp;
+  if (route == DV_GN_STAT16) g.stats16 = sbuf;
+  if (route == DV_GN_SLAB) g.stats = sbuf;
+  hipError_t e = launch_gemm(g, DV_PREC_BF16X3, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: launch failed: %s", hipGetErrorString(e));
+  if (route == DV_GN_KSTAT16) {
+    e = launch_stat16(y, sbuf, M, C, st);
+    if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: k_stat16 launch failed: %s", hipGetErrorString(e));
+  }
+  GnApplyParams gp{};
+  gp.a0 = y; gp.c0 = C;
+  if (route == DV_GN_SLAB) gp.slab0 = sbuf; else gp.st16_0 = sbuf;
+  gp.gamma = gamma; gp.beta = beta; gp.eps = eps; gp.groups = G;
+  gp.out_hi = y_norm_hi; gp.out_lo = y_norm_lo; gp.B = B; gp.T = Tp; gp.Tv = T;
+  e = launch_gn_apply(gp, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: k_gn_apply refused C = %d, G = %d, T = %d, Tp = %d on this route: %s", C, G, T, Tp, hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}

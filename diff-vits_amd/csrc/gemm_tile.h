@@ -1005,9 +1005,15 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
       if (p.stats) {
         // column sums over this 32-row block: 16 values per lane summed across the 32 lanes of each half by a
         // halving butterfly (8 + 4 + 2 + 1 exchanges, then one add with the neighbour lane)
+        // Both sums run on values SHIFTED by the column's value in the block's first row: fp32 sums of raw squares lose
+        // mean^2 / var of their precision (a column at 300 sigma: rstd 1e-3 off), sums of (v - k)^2 do not.  The words leave as
+        // (sum, squared deviations from the column's own mean in the block) - the 32x16 blocks' form, one column wide.
         float s1[16], s2[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { s1[r] = vv[r]; s2[r] = vv[r] * vv[r]; }
+        for (int r = 0; r < 16; ++r) {
+          const float d = m_ok ? vv[r] - __shfl(vv[r], lane & 32) : 0.f;
+          s1[r] = d; s2[r] = d * d;
+        }
 #pragma unroll
         for (int w = 8; w >= 1; w >>= 1) {
           const bool up = (l31 & (2 * w)) != 0;      // lane keeps the upper half of its 2w values
@@ -1023,8 +1029,13 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
         s2[0] += __shfl_xor(s2[0], 1);
         const int r = (l31 >> 1) & 15;               // bit 4 -> r bit 3, ... bit 1 -> r bit 0
         const int n = nf + 8 * (r >> 2) + (r & 3);
+        float kk = 0.f;                              // the shift of this lane's column (the first row's lane holds all 16)
+#pragma unroll
+        for (int r2 = 0; r2 < 16; ++r2) { const float k0 = __shfl(vv[r2], lane & 32); kk = r2 == r ? k0 : kk; }
+        const float cnt = (float)(padded ? blk_cnt(mrow0) : min(32, p.M - mrow0));   // rows of the block that exist
         if ((l31 & 1) == 0 && n < p.N && mrow0 < p.M)
-          reinterpret_cast<float2*>(p.stats)[(size_t)(mrow0 >> 5) * p.N + n] = make_float2(s1[0], s2[0]);
+          reinterpret_cast<float2*>(p.stats)[(size_t)(mrow0 >> 5) * p.N + n] =
+              make_float2(fmaf(cnt, kk, s1[0]), fmaxf(s2[0] - s1[0] * s1[0] / cnt, 0.f));
       }
 #if !DV_GNX_STATS_FIRST
       if (p.stats16) {

@@ -129,7 +129,7 @@ __device__ __forceinline__ void gn_apply_body(const GnApplyParams& p, int rows_p
       const int ld = first ? p.c0 : p.c1, cc = first ? c : c - p.c0;
       const float2 v = ld_mut2<SC1>(slab + (size_t)(b * RB + rb) * ld + cc);
       s1 += v.x;
-      s2 += v.y;
+      s2 += (double)v.y + (double)v.x * (double)v.x / (double)min(32, p.T - 32 * rb);   // = the column's sum of squares in the block
     }
     s1 = wave_sum_d(s1);
     s2 = wave_sum_d(s2);

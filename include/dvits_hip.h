@@ -532,6 +532,55 @@ int dv_op_cfg_pair_in(const float* in, float* out, int64_t numel, void* stream);
 int dv_op_known_frames(float* x_inout, const float* known, const float* eps, const uint8_t* keep,
                        int32_t rows, int32_t channels, int32_t frames, double alpha, double sigma, void* stream);
 
+/* ---- normalisation on the kernels the forward runs (tests/test_gpu_norm_ops.py).  All pointers are device pointers; every
+ * argument is checked before anything is launched (DV_ERR_INVALID), the call returns after the stream has drained. ---- */
+/* LayerNorm over the last axis of x [M, C] float32 (biased variance, two passes on register-resident rows), C a multiple of 4 up
+ * to 2048 (anything else is an error, there is no other kernel), x / gamma / beta / outputs 16-byte aligned.  route:
+ *   DV_LN_STATS   k_ln_rows<false>: mean [M], rstd [M] only; every other pointer NULL.
+ *   DV_LN_ROWS    k_ln_rows<true>: y [M, C] = (x - mean) * rstd * gamma + beta; gamma, beta, y only.
+ *   DV_LN_APPLY   k_ln_apply: y_hi / y_lo [M, C] = split planes of (x - mean) * rstd, no affine (y_lo may be NULL); gamma = beta = NULL.
+ *   DV_LN_AFFINE  k_ln_affine: (fma((x - mean) * rstd, gamma, beta)) * rowmask[row] (rowmask [M] or NULL) -> y and / or planes. */
+enum { DV_LN_STATS = 0, DV_LN_ROWS = 1, DV_LN_APPLY = 2, DV_LN_AFFINE = 3 };
+int dv_op_layer_norm(const float* x, const float* gamma, const float* beta, const float* rowmask, float* y, uint16_t* y_hi,
+                     uint16_t* y_lo, float* mean, float* rstd, int32_t M, int32_t C, float eps, int32_t route, void* stream);
+/* k_ln_rows<true> with the row re-mapping of the pooled-text sequence: x holds M / rows_per_batch utterances of rows_per_batch
+ * rows; row r of utterance b goes to row b * out_rows_per_batch + out_row_off + r of y [M / rows_per_batch * out_rows_per_batch,
+ * C].  The other rows of y are not written.  0 <= out_row_off <= out_rows_per_batch - rows_per_batch, M % rows_per_batch == 0. */
+int dv_op_layer_norm_into(const float* x, const float* gamma, const float* beta, float* y, int32_t M, int32_t C, float eps,
+                          int32_t rows_per_batch, int32_t out_rows_per_batch, int32_t out_row_off, void* stream);
+/* The prompt encoder's input stage (k_prompt_pre): prompt [B, C, L] channels-first, keep [B, L] (0 = padding frame: its channels
+ * are read as zeros), LayerNorm(C) with affine -> split planes hi / lo [B * L, cpad] (lo may be NULL), columns [C, cpad) zero,
+ * key_bias [B, L] = keep ? 0 : -1e30.  A padding frame is a constant row: its planes hold beta.  1 <= C <= cpad <= 512. */
+int dv_op_prompt_pre(const float* prompt, const float* keep, const float* gamma, const float* beta, uint16_t* hi, uint16_t* lo,
+                     float* key_bias, int32_t B, int32_t C, int32_t L, int32_t cpad, float eps, void* stream);
+/* LayerNorm fused across two contractions, as the transformer blocks run it (eps 1e-5):
+ *   producer  y1 [M, C] = x [M, K] w1 [C, K]^T + b1 (+ res [M, C]); b1, res may be NULL
+ *   consumer  y2 [M, N] = LayerNorm(y1; gamma, beta) w2 [N, C]^T + b2 (b2 may be NULL)
+ * fused = 1: the producer's epilogue also writes the raw split planes of y1 and rowstat [M, C / 32, 2] - per 32-column block of a
+ * row (sum, squared deviations from the block's own mean) -; the consumer multiplies the raw planes by the gamma-folded weights
+ * and finishes rstd * (acc - mean * u) + b' from the partials in its epilogue.  fused = 0: k_ln_apply normalises y1 into planes
+ * between the two launches (the DVITS_FUSE_LN=0 schedule); rowstat is not written and may be NULL.  Both routes use the weights
+ * as the engine packs them: gamma folded into w2's planes, u[n] = sum_c gamma[c] w2[n, c], beta folded into the bias.
+ * K a multiple of 32; C a multiple of 32 up to 512 (the consumer holds at most 16 partials per row). */
+int dv_op_linear_ln(const float* x, const float* w1, const float* b1, const float* res, const float* gamma, const float* beta,
+                    const float* w2, const float* b2, int32_t M, int32_t K, int32_t C, int32_t N, int32_t fused, float* y1,
+                    float* rowstat, float* y2, void* stream);
+/* GroupNorm behind a k = 1 contraction in the padded row space of dv_op_conv3 (T frames of B utterances, row pitch Tp a multiple
+ * of 32, T > Tp - 32): y [B * Tp, C] = x [B * Tp, K] w [C, K]^T + b (b may be NULL; rows [T, Tp) of x may hold anything finite,
+ * the same rows of y are written as zeros), then k_gn_apply (no time scale / shift, no SiLU) -> split planes y_norm_hi / _lo
+ * [B * Tp, C] of (y - mean) * rstd * gamma + beta over G groups of channels and the T frames of an utterance (padding rows: beta -
+ * mean * rstd * gamma, of no meaning).  route says who writes the statistics k_gn_apply reduces:
+ *   DV_GN_STAT16   the GEMM epilogue: per (32-row, 16-column) block (sum, squared deviations from the block's own mean over the
+ *                  rows that exist), stats [B * Tp / 32, C / 16, 2].  C / G a multiple of 16.
+ *   DV_GN_SLAB     the GEMM epilogue: per 32-row block and column (sum, squared deviations from the column's own mean in the
+ *                  block), stats [B * Tp / 32, C, 2].  C / G a multiple of 4; T == Tp (the slab has no padded-row form).
+ *   DV_GN_KSTAT16  no statistics in the epilogue; the standalone k_stat16 computes DV_GN_STAT16's words from y.  T == Tp.
+ * stats (NULL: not wanted) receives those words.  K a multiple of 32; G <= 64; C / G <= 512. */
+enum { DV_GN_STAT16 = 0, DV_GN_SLAB = 1, DV_GN_KSTAT16 = 2 };
+int dv_op_linear_gn(const float* x, const float* w, const float* b, const float* gamma, const float* beta, int32_t B, int32_t T,
+                    int32_t Tp, int32_t K, int32_t C, int32_t G, float eps, int32_t route, float* y, float* stats,
+                    uint16_t* y_norm_hi, uint16_t* y_norm_lo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

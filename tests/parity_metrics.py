@@ -337,22 +337,34 @@ def _linear(x, W, b, emulate):
     return F.linear(_planes(x), _planes(W), b) if emulate else F.linear(x, W, b)
 
 
-def ln_linear(x, gamma, beta, W, b, emulate=False, fault=None, eps=1e-5):
+def ln_linear(x, gamma, beta, W, b, emulate=False, fault=None, eps=1e-5, stats=None, acc32=False):
     """linear(LayerNorm(x) gamma + beta; W, b) in fp64, or (emulate / fault) in the folded form described above.  Faults:
     "lost_lo" - the raw row enters the contraction as its hi plane alone; "mean_from_bf16" - the row mean is taken from the
-    bf16-rounded row, not from the fp32 row; "beta_sign" - beta folded into b' with the wrong sign."""
+    bf16-rounded row, not from the fp32 row; "beta_sign" - beta folded into b' with the wrong sign.
+    stats = (mean, rstd) per row: the folded form finishes with THESE (what the consumer combined from the producer's fp32
+    partials: tests/norm_cases.py) instead of the fp64 statistics of the row.  acc32: u, b' and the contraction are rounded to
+    float32 and the finish rstd * (acc - mean * u) + b' runs in float32, as the epilogue does."""
     import torch.nn.functional as F
     x = torch.as_tensor(x).double()
-    if not emulate and fault not in ("lost_lo", "mean_from_bf16", "beta_sign"):
+    if not emulate and stats is None and fault not in ("lost_lo", "mean_from_bf16", "beta_sign"):
         return F.linear(F.layer_norm(x, (x.shape[-1],), gamma, beta, eps), W, b)
     x32 = x.float().double()
     mean = x32.mean(-1, keepdim=True)
     rstd = 1.0 / torch.sqrt(((x32 - mean) ** 2).mean(-1, keepdim=True) + eps)
+    if stats is not None:
+        mean, rstd = (torch.as_tensor(s).double().reshape(-1, 1) for s in stats)
     if fault == "mean_from_bf16":
         mean = _planes(x, lo=False).mean(-1, keepdim=True)
     Wf = _planes(W * gamma[None, :])
     bf = (-1.0 if fault == "beta_sign" else 1.0) * (W @ beta) + (0.0 if b is None else b)
-    return rstd * (_planes(x, lo=fault != "lost_lo") @ Wf.t() - mean * Wf.sum(-1)) + bf
+    xp = _planes(x, lo=fault != "lost_lo")
+    if acc32:    # the three products of the split-bf16 contraction (hi hi + hi lo + lo hi; lo lo is never formed), float32 accumulation
+        u32, b32 = (W * gamma[None, :]).sum(-1).float(), bf.float()
+        xh, wh = _planes(x, lo=False).float(), _planes(W * gamma[None, :], lo=False).float()
+        xl, wl = (xp.float() - xh) if fault != "lost_lo" else torch.zeros_like(xh), Wf.float() - wh
+        acc = xh @ wh.t() + xh @ wl.t() + xl @ wh.t()
+        return (rstd.float() * (acc - mean.float() * u32) + b32).double()
+    return rstd * (xp @ Wf.t() - mean * Wf.sum(-1)) + bf
 
 
 def _sdpa(q, k, v, heads, bias, emulate):
