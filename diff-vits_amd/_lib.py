@@ -117,6 +117,8 @@ SIGNATURES = {
     "dv_op_conv1d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p]),
     "dv_op_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
     "dv_op_linear_planes": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 6 + [C.c_void_p]),
+    "dv_op_gemm": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 11 + [C.c_void_p]),
+    "dv_op_gemm_variant": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_int32)] * 3),
     "dv_op_group_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),
     "dv_op_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_attention_frag": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
@@ -129,6 +131,11 @@ SIGNATURES = {
 }
 LN_STATS, LN_ROWS, LN_APPLY, LN_AFFINE = 0, 1, 2, 3
 GN_STAT16, GN_SLAB, GN_KSTAT16 = 0, 1, 2
+# k_gemm's tile menu (DV_GT_*), epilogues (DV_GEMM_*) and the fused split-K flag of dv_op_gemm
+GT = {"auto": 0, "T0": 1, "T1": 2, "T2": 3, "T2S": 4, "T2G": 5, "T3": 6, "T4": 7, "T4G": 8, "T0S": 9}
+GT_BK64 = 0x100
+GEMM_STORE, GEMM_RESIDUAL, GEMM_GEGLU = 0, 1, 2
+GEMM_SPLITK_FUSED = 0x100
 
 _lib = None
 

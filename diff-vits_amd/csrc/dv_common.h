@@ -125,7 +125,8 @@ int gemm_gnx_plan(const GemmParams& p, int n_cu);
 // grids above the CU count may carry waiting hand-overs when one utterance's share of an XCD fits its CUs (kernels_gemm.hip)
 bool gemm_handover_rounds();
 // tile menu ids (kernels_gemm.hip); GT_BK64 is or-ed in when the tile runs 64-deep k-tiles
-enum { GT_AUTO = 0, GT_T0 = 1, GT_T1 = 2, GT_T2 = 3, GT_T2S = 4, GT_T2G = 5, GT_T3 = 6, GT_T4 = 7, GT_T4G = 8,
+// (GT_T0 / GT_T0S are 32-deep only: launch_gemm refuses them with GT_BK64)
+enum { GT_AUTO = 0, GT_T0 = 1, GT_T1 = 2, GT_T2 = 3, GT_T2S = 4, GT_T2G = 5, GT_T3 = 6, GT_T4 = 7, GT_T4G = 8, GT_T0S = 9,
        GT_BK64 = 0x100 };
 // candidate tiles (force_tile values) that can run this GEMM; returns the count written to out[cap]
 int gemm_candidates(const GemmParams& p, int* out, int cap);
@@ -483,6 +484,11 @@ hipError_t launch_regulate_sample(const float* m_p, const float* logs_p, const i
                                   float* logs_exp, hipStream_t st);
 // k_gemm instantiation launch_gemm picks for a plain GEMM: BM | BN << 8 | BK << 16 | k-groups << 24 (kernels_gemm.hip)
 int gemm_variant(const GemmParams& p);
+// GT_* tile of the menu that variant `v` (gemm_variant's result for p) is launched on: the forced tile, or the one
+// Tiles<BK>::launch_variant dispatches the heuristic's choice to; -1 if none
+int gemm_variant_tile(const GemmParams& p, int v);
+// true where tile `gt` (GT_*, without GT_BK64) keeps a 64-column block inside one wave (two column fragments): what EPI_GEGLU needs
+bool gemm_tile_geglu_ok(int gt);
 // enrolled voices (kernels_voice.hip): one batch row of every conditioning segment <-> a voice record.  segs_dev: the device copy
 // of the segment table (sorted by chunk0; a segment of `bytes` per utterance owns ceil(bytes / 16) chunks of the record), chunks:
 // 16-byte chunks of one record; rows / recs: HOST arrays of n (batch row, record address) pairs - they travel in the launch's

@@ -2844,6 +2844,119 @@ extern "C" int dv_op_linear_planes(const float* x, const float* w, const float* 
                    "dv_op_linear_planes");
 }
 
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// ---- dv_op_gemm: k_gemm on a chosen menu entry, k-split form, epilogue and source layout (include/dvits_hip.h) ----
+static_assert(DV_GT_AUTO == GT_AUTO && DV_GT_T0 == GT_T0 && DV_GT_T1 == GT_T1 && DV_GT_T2 == GT_T2 && DV_GT_T2S == GT_T2S && DV_GT_T2G == GT_T2G &&
+              DV_GT_T3 == GT_T3 && DV_GT_T4 == GT_T4 && DV_GT_T4G == GT_T4G && DV_GT_T0S == GT_T0S && DV_GT_BK64 == GT_BK64, "public tile ids");
+static_assert(DV_GEMM_STORE == EPI_STORE && DV_GEMM_RESIDUAL == EPI_RESIDUAL && DV_GEMM_GEGLU == EPI_GEGLU, "public epilogue ids");
+
+// Checks everything launch_gemm / k_gemm need of the shape and fills the host-only fields of g (no pointers, nothing launched): the
+// requirements are read from gemm_tile.h and launch_gemm, never found by launching.  0, or DV_ERR_INVALID with the message set.
+static int gemm_op_shape(GemmParams& g, int M, int K, int N, int K0, int epi, int tile, int splitk, int precision, const char* what) {
+  if (M <= 0 || N <= 0 || K <= 0 || M > 32768 || N > 32768) return dv_fail(DV_ERR_INVALID, "%s: M = %d, N = %d, K = %d: 1 .. 32768 rows and columns", what, M, N, K);
+  if (precision != DV_PREC_BF16X3 && precision != DV_PREC_BF16) return dv_fail(DV_ERR_INVALID, "%s: precision %d is not a DV_PREC_*", what, precision);
+  if (epi != DV_GEMM_STORE && epi != DV_GEMM_RESIDUAL && epi != DV_GEMM_GEGLU) return dv_fail(DV_ERR_INVALID, "%s: epilogue %d is not a DV_GEMM_*", what, epi);
+  if (K0 < 0 || K0 >= K) return dv_fail(DV_ERR_INVALID, "%s: K0 = %d must be 0 or inside (0, K = %d)", what, K0, K);
+  const int c0 = K0 > 0 ? K0 : K, c1 = K0 > 0 ? K - K0 : 0;
+  if (c0 % 32 != 0 || c1 % 32 != 0) return dv_fail(DV_ERR_INVALID, "%s: source widths %d and %d must be multiples of 32 (the k-tile)", what, c0, c1);
+  if (2 * (size_t)c0 + 256 > DV_ZERO_PAGE_BYTES || 2 * (size_t)c1 + 256 > DV_ZERO_PAGE_BYTES)
+    return dv_fail(DV_ERR_INVALID, "%s: a source of %d channels exceeds the %d one source tensor may have", what, c0 > c1 ? c0 : c1, (DV_ZERO_PAGE_BYTES - 256) / 2);
+  const int ft = tile & 0xff;
+  if ((tile & ~(0xff | GT_BK64)) != 0 || ft > GT_T0S || (ft == GT_AUTO && tile != 0)) return dv_fail(DV_ERR_INVALID, "%s: tile 0x%x is not 0 or a DV_GT_* id (| DV_GT_BK64)", what, tile);
+  if (tile & GT_BK64) {
+    if (ft == GT_T0 || ft == GT_T0S) return dv_fail(DV_ERR_INVALID, "%s: the 128x128 tiles exist with 32-deep k-tiles only", what);
+    if (c0 % 64 != 0 || c1 % 64 != 0) return dv_fail(DV_ERR_INVALID, "%s: 64-deep k-tiles need source widths that are multiples of 64, not %d and %d", what, c0, c1);
+  }
+  if (epi == DV_GEMM_GEGLU) {
+    if (N % 64 != 0) return dv_fail(DV_ERR_INVALID, "%s: GEGLU needs N %% 64 == 0 ([32 value | 32 gate] column blocks), not N = %d", what, N);
+    if (ft != GT_AUTO && !gemm_tile_geglu_ok(ft)) return dv_fail(DV_ERR_INVALID, "%s: GEGLU needs a tile with a 64-column block per wave (T0, T0S, T1, T2G, T4G), not tile %d", what, ft);
+  }
+  const int fused = splitk & DV_GEMM_SPLITK_FUSED, slices = splitk & ~DV_GEMM_SPLITK_FUSED;
+  if (splitk != 0) {
+    if (fused ? slices != 2 : (slices != 2 && slices != 3)) return dv_fail(DV_ERR_INVALID, "%s: splitk 0x%x: 2 or 3 slices in two launches, or 2 | DV_GEMM_SPLITK_FUSED", what, splitk);
+    if (epi == DV_GEMM_GEGLU) return dv_fail(DV_ERR_INVALID, "%s: split-K runs the store and residual epilogues only (gemm_splitk_plan)", what);
+    if (K / 64 < slices) return dv_fail(DV_ERR_INVALID, "%s: K = %d has fewer 64-deep k-tiles than the %d slices", what, K, slices);
+    if (fused && ((M + 31) / 32) * ((N + 31) / 32) > 4096) return dv_fail(DV_ERR_INVALID, "%s: the fused pair has 4096 tile counters; M = %d, N = %d need more", what, M, N);
+  }
+  g = GemmParams{};
+  g.seg[0].c0 = c0; g.seg[0].c1 = c1; g.seg[0].taps = 1;
+  g.nseg = 1; g.B = 1; g.T_in = g.T_out = g.T_virt = M; g.stride = 1;
+  g.Kp = K; g.N_pad = rup(N, 128); g.M = M; g.N = N; g.epi = epi; g.force_tile = tile;
+  return DV_OK;
+}
+
+extern "C" int dv_op_gemm_variant(int32_t M, int32_t K, int32_t N, int32_t K0, int32_t epi, int32_t tile, int32_t splitk, int32_t precision,
+                                  int32_t* variant, int32_t* tile_kind, int32_t* nsplit) {
+  if (!variant || !tile_kind || !nsplit) return dv_fail(DV_ERR_INVALID, "dv_op_gemm_variant: null argument");
+  GemmParams g;
+  if (int rc = gemm_op_shape(g, M, K, N, K0, epi, tile, splitk, precision, "dv_op_gemm_variant")) return rc;
+  const int v = gemm_variant(g);
+  const int kind = gemm_variant_tile(g, v);
+  if (v < 0 || kind < 0) return dv_fail(DV_ERR_INVALID, "dv_op_gemm_variant: no instantiation for tile 0x%x", tile);
+  *variant = v; *tile_kind = kind; *nsplit = precision == DV_PREC_BF16X3 ? 3 : 1;
+  return DV_OK;
+}
+
+extern "C" int dv_op_gemm(const float* x, const float* w, const float* bias, const float* res, const float* rowmask, float* y, uint16_t* y_hi,
+                          uint16_t* y_lo, int32_t M, int32_t K, int32_t N, int32_t K0, int32_t ldo, int32_t ldres, int32_t epi, int32_t relu,
+                          int32_t tile, int32_t splitk, int32_t precision, void* stream) {
+  const char* what = "dv_op_gemm";
+  GemmParams g;
+  if (int rc = gemm_op_shape(g, M, K, N, K0, epi, tile, splitk, precision, what)) return rc;
+  const bool x3 = precision == DV_PREC_BF16X3;
+  if (!x || !w || (!y && !y_hi)) return dv_fail(DV_ERR_INVALID, "%s: x, w and an output (y and / or y_hi) are required", what);
+  if (y_hi && x3 && !y_lo) return dv_fail(DV_ERR_INVALID, "%s: bf16x3 plane output needs y_lo", what);
+  if (!y_hi && y_lo) return dv_fail(DV_ERR_INVALID, "%s: y_lo without y_hi", what);
+  const int n_out = epi == DV_GEMM_GEGLU ? N / 2 : N;
+  if (ldo < n_out) return dv_fail(DV_ERR_INVALID, "%s: ldo %d < %d output columns", what, ldo, n_out);
+  if (epi == DV_GEMM_RESIDUAL ? (!res || ldres < N) : (res != nullptr)) return dv_fail(DV_ERR_INVALID, "%s: res [M, ldres >= N] goes with DV_GEMM_RESIDUAL, and only with it", what);
+  if (relu != 0 && relu != 1) return dv_fail(DV_ERR_INVALID, "%s: relu is 0 or 1", what);
+  if (epi == DV_GEMM_GEGLU && (relu || rowmask)) return dv_fail(DV_ERR_INVALID, "%s: the GEGLU epilogue has no ReLU / row mask", what);
+  // 16-byte epilogue accesses are taken on the pitches alone (gemm_tile.h vec4 / al8): the bases must allow them
+  if (!al16(y) || !al16(res) || !al16(y_hi) || !al16(y_lo) || !al16(x)) return dv_fail(DV_ERR_INVALID, "%s: x, res and the outputs must be 16-byte aligned", what);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(gemm_init());
+  gemm_env_refresh();
+  HIPCHK(attn_init());
+  const int c0 = g.seg[0].c0, c1 = g.seg[0].c1, Npad = g.N_pad;
+  const int fused = splitk & DV_GEMM_SPLITK_FUSED, slices = splitk & ~DV_GEMM_SPLITK_FUSED;
+  OpScratch sc;
+  bf16_t* xh = sc.get<bf16_t>((size_t)M * K * 2, st, false);
+  bf16_t* xl = x3 ? sc.get<bf16_t>((size_t)M * K * 2, st, false) : nullptr;
+  bf16_t* hi = sc.get<bf16_t>((size_t)Npad * K * 2, st, true);
+  bf16_t* lo = x3 ? sc.get<bf16_t>((size_t)Npad * K * 2, st, true) : nullptr;
+  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
+  const bool geglu = epi == DV_GEMM_GEGLU;
+  float* pb = (geglu && bias) ? sc.get<float>((size_t)Npad * 4, st, true) : nullptr;
+  float* xs = c1 > 0 ? sc.get<float>((size_t)M * K * 4, st, false) : nullptr;   // the two sources, each contiguous: [M, c0] then [M, c1]
+  float* skb = slices ? sc.get<float>(gemm_splitk_bytes(M, N, slices), st, false) : nullptr;
+  unsigned* skt = fused ? sc.get<unsigned>(4096 * sizeof(unsigned), st, true) : nullptr;
+  if (!xh || !hi || !zp || (x3 && (!xl || !lo)) || (geglu && bias && !pb) || (c1 > 0 && !xs) || (slices && !skb) || (fused && !skt))
+    return dv_fail(DV_ERR_HIP, "%s: hipMalloc failed", what);
+  if (c1 > 0) {
+    HIPCHK(hipMemcpy2DAsync(xs, (size_t)c0 * 4, x, (size_t)K * 4, (size_t)c0 * 4, M, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(xs + (size_t)M * c0, (size_t)c1 * 4, x + c0, (size_t)K * 4, (size_t)c1 * 4, M, hipMemcpyDeviceToDevice, st));
+    HIPCHK(launch_split(xs, xh, xl, (int64_t)M * K, st));     // (elementwise: the planes keep the [M, c0] | [M, c1] layout)
+  } else {
+    HIPCHK(launch_split(x, xh, xl, (int64_t)M * K, st));
+  }
+  PackSpec s{};
+  s.src = w; s.N = N; s.kind = 0; s.C = K; s.taps = 1; s.c_pad = K; s.geglu = geglu;
+  HIPCHK(launch_pack_weight(s, hi, lo, K, st));
+  if (pb) HIPCHK(launch_fold_bias(nullptr, bias, nullptr, pb, N, K, 0, 1, st));   // bias in the packed [32 value | 32 gate] column order
+  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl;
+  if (c1 > 0) { g.seg[0].a1_hi = xh + (size_t)M * c0; g.seg[0].a1_lo = xl ? xl + (size_t)M * c0 : nullptr; }
+  g.w_hi = hi; g.w_lo = lo; g.bias = geglu ? pb : bias; g.zero_page = zp;
+  g.res = res; g.ldres = ldres; g.relu = relu; g.rowmask = rowmask;
+  g.out = y; g.out_hi = reinterpret_cast<bf16_t*>(y_hi); g.out_lo = x3 ? reinterpret_cast<bf16_t*>(y_lo) : nullptr; g.ldo = ldo;
+  if (slices) { g.sk_buf = skb; g.sk_split = slices; g.sk_ticket = skt; }
+  hipError_t e = launch_gemm(g, precision, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
 extern "C" int dv_op_group_stats(const float* x, float* mean, float* rstd, int32_t B, int32_t T, int32_t C, int32_t groups,
                                  float eps, void* stream) {
   if (!x || !mean || !rstd || C % groups != 0 || (C / groups) % 4 != 0 || groups > 64)
@@ -2972,7 +3085,6 @@ extern "C" int dv_op_conv3(const float* x, const float* w, const float* bias, co
 
 // ----------------------------------------------------------------------------- normalisation entry points
 // The LayerNorm / GroupNorm routes of the forward through the launchers the engine calls (include/dvits_hip.h).
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int dv_op_layer_norm(const float* x, const float* gamma, const float* beta, const float* rowmask, float* y, uint16_t* y_hi,
                                 uint16_t* y_lo, float* mean, float* rstd, int32_t M, int32_t C, float eps, int32_t route, void* stream) {

@@ -145,6 +145,7 @@ template <int BK> struct Tiles {
   static hipError_t launch_forced(const GemmParams& p, bool x3, int tile, hipStream_t st) {
     switch (tile) {
       case GT_T0: return T0::launch(p, x3, st);
+      case GT_T0S: return T0S::launch(p, x3, st);
       case GT_T1: return T1::launch(p, x3, st);
       case GT_T2: return T2::launch(p, x3, st);
       case GT_T2S: return T2S::launch(p, x3, st);
@@ -252,6 +253,7 @@ int gemm_variant(const GemmParams& p) {
     const int bk = (p.force_tile & GT_BK64) ? 64 : 32, kg2 = bk == 64 ? 2 : 1;
     switch (ft) {
       case GT_T0: return id(128, 128, 32, 2);
+      case GT_T0S: return id(128, 128, 32, 1);
       case GT_T1: return id(128, 64, bk, kg2);
       case GT_T2: return id(64, 64, bk, kg2);
       case GT_T2S: return id(64, 64, bk, 1);
@@ -277,6 +279,23 @@ int gemm_variant(const GemmParams& p) {
   if (cnt(64, 32) >= min_wg) return id(64, 32, bk, kg2);
   return id(32, 32, bk, kg2);
 }
+
+// The menu entry behind a variant id: mirrors Tiles<BK>::launch_variant (heuristic) / launch_forced (forced tile)
+int gemm_variant_tile(const GemmParams& p, int v) {
+  if (v < 0) return -1;
+  const int ft = p.force_tile & 0xff;
+  if (ft != GT_AUTO) return ft;
+  const int bm = v & 255, bn = (v >> 8) & 255, bk = (v >> 16) & 255, kg = v >> 24;
+  if (bm == 128 && bn == 128) return kg == 2 ? GT_T0 : GT_T0S;
+  if (bm == 128 && bn == 64) return GT_T1;
+  if (bm == 64 && bn == 64) return p.epi == EPI_GEGLU ? GT_T2G : ((bk == 64 && kg == 2) ? GT_T2 : GT_T2S);
+  if (bm == 64 && bn == 32) return GT_T3;
+  if (bm == 32 && bn == 32) return GT_T4;
+  if (bm == 32 && bn == 64) return GT_T4G;
+  return -1;
+}
+// FN == 2 tiles of Tiles<BK> (BN / (WN * 32)): 128x128 on 2x2 waves, 128x64 on 4x1, 64x64 on 2x1, 32x64 on 1x1
+bool gemm_tile_geglu_ok(int gt) { return gt == GT_T0 || gt == GT_T0S || gt == GT_T1 || gt == GT_T2G || gt == GT_T4G; }
 
 // XCD rectangle of a tm x tn tile grid run as xs k-slices (fills p.xcd_*; xcd_n = 0: row bands of the tile grid)
 static void gemm_xcd_rect(GemmParams& p, int tm, int tn, int xs) {
@@ -433,6 +452,9 @@ hipError_t launch_gemm(const GemmParams& pin, int precision, hipStream_t st) {
   for (int s = 0; s < p.nseg; ++s) k64 = k64 && p.seg[s].c0 % 64 == 0 && p.seg[s].c1 % 64 == 0;
   const int ft = p.force_tile & 0xff;
   if (ft != GT_AUTO && (p.force_tile & GT_BK64) && !k64) return hipErrorInvalidValue;
+  // (the 128x128 tiles are compiled 32 deep only: with GT_BK64 the k-tile count below would be that of 64-deep tiles - half the sum)
+  if ((ft == GT_T0 || ft == GT_T0S) && (p.force_tile & GT_BK64)) return hipErrorInvalidValue;
+  if (ft != GT_AUTO && p.epi == EPI_GEGLU && !gemm_tile_geglu_ok(ft)) return hipErrorInvalidValue;   // (the epilogue would store nothing)
   const int variant = gemm_variant(p);
   if (variant < 0) return hipErrorInvalidValue;
   const int bk = ft != GT_AUTO ? ((p.force_tile & GT_BK64) ? 64 : 32) : (variant >> 16) & 255;

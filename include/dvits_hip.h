@@ -487,6 +487,32 @@ int dv_op_linear(const float* x, const float* w, const float* bias, float* y, in
  * the planes receive N_out columns of value * gelu(gate), y must be NULL. */
 int dv_op_linear_planes(const float* x, const float* w, const float* bias, float* y, uint16_t* y_hi, uint16_t* y_lo, int32_t M,
                         int32_t K, int32_t N, int32_t ldo, int32_t geglu, int32_t precision, void* stream);
+/* The general form of dv_op_linear*: y[M, ldo] = epi(x[M, K] @ w[N, K]^T + bias) on a chosen entry of k_gemm's tile menu.
+ *   tile     DV_GT_AUTO (the shape heuristic of the forward) or a DV_GT_* tile, optionally | DV_GT_BK64 (64-deep k-tiles on two
+ *            k-groups; the 128x128 tiles are 32 deep only) - what the prepare-time tuner sets
+ *   epi      DV_GEMM_STORE; DV_GEMM_RESIDUAL: + res[M, ldres >= N]; DV_GEMM_GEGLU: w = [value rows | gate rows], N % 64 == 0, N / 2
+ *            output columns of value * gelu(gate), only on the tiles with a 64-column block per wave (T0, T0S, T1, T2G, T4G)
+ *   relu     1: max(., 0) after bias / residual;  rowmask[M] (or NULL): multiplies every row after it.  Not with GEGLU.
+ *   K0       0, or 0 < K0 < K: the first K0 columns of x become source 0 and the rest source 1 of one k-segment (the channel
+ *            concatenation of the up path).  Every source width is a multiple of 32, of 64 with DV_GT_BK64.
+ *   splitk   0; 2 or 3: that many k-slices dumped by one launch and summed by an epilogue-only second; 2 | DV_GEMM_SPLITK_FUSED:
+ *            both halves and the epilogue in one launch.  Store and residual epilogues only, K / 64 >= slices.
+ *   outputs  fp32 y and / or split bf16 planes y_hi, y_lo (uint16 bit patterns; y_lo is ignored in bf16 mode), all [M, ldo];
+ *            x, res and the outputs 16-byte aligned.
+ * Every argument is checked before anything is launched (DV_ERR_INVALID with a message: a combination the kernel cannot run is
+ * never launched); returns after the stream has drained. */
+enum { DV_GT_AUTO = 0, DV_GT_T0 = 1, DV_GT_T1 = 2, DV_GT_T2 = 3, DV_GT_T2S = 4, DV_GT_T2G = 5, DV_GT_T3 = 6, DV_GT_T4 = 7, DV_GT_T4G = 8,
+       DV_GT_T0S = 9, DV_GT_BK64 = 0x100 };
+enum { DV_GEMM_STORE = 0, DV_GEMM_RESIDUAL = 1, DV_GEMM_GEGLU = 2 };
+enum { DV_GEMM_SPLITK_FUSED = 0x100 };
+int dv_op_gemm(const float* x, const float* w, const float* bias, const float* res, const float* rowmask, float* y, uint16_t* y_hi,
+               uint16_t* y_lo, int32_t M, int32_t K, int32_t N, int32_t K0, int32_t ldo, int32_t ldres, int32_t epi, int32_t relu,
+               int32_t tile, int32_t splitk, int32_t precision, void* stream);
+/* Which instantiation dv_op_gemm would launch for these arguments (host only, the same checks): variant = BM | BN << 8 | BK << 16 |
+ * k-groups << 24, tile_kind = its DV_GT_* menu entry (the heuristic's choice resolved), nsplit = 3 (split bf16: three products per
+ * k-step) or 1 (single bf16). */
+int dv_op_gemm_variant(int32_t M, int32_t K, int32_t N, int32_t K0, int32_t epi, int32_t tile, int32_t splitk, int32_t precision,
+                       int32_t* variant, int32_t* tile_kind, int32_t* nsplit);
 /* GroupNorm statistics over a channels-last tensor x[B*T, C]: mean/rstd [B, groups]. */
 int dv_op_group_stats(const float* x, float* mean, float* rstd, int32_t B, int32_t T, int32_t C, int32_t groups,
                       float eps, void* stream);
