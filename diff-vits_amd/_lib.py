@@ -36,6 +36,11 @@ class TencCfg(C.Structure):
                                          "n_heads", "n_layers", "kernel_size", "window_size", "gin_channels", "cond_layer_idx")]
 
 
+class QencCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("in_channels", "out_channels", "hidden_channels", "kernel_size", "dilation_rate", "n_layers",
+                                         "gin_channels")]
+
+
 MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p)
 
 # every symbol include/dvits_hip.h declares: (restype, argtypes)
@@ -74,6 +79,14 @@ SIGNATURES = {
     "dv_tenc_forward": (C.c_int, [C.c_void_p] * 10),
     "dv_tenc_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "dv_tenc_probe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "dv_qenc_create": (C.c_int, [C.POINTER(QencCfg), C.POINTER(C.c_void_p)]),
+    "dv_qenc_destroy": (None, [C.c_void_p]),
+    "dv_qenc_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "dv_qenc_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "dv_qenc_forward": (C.c_int, [C.c_void_p] * 9),
+    "dv_qenc_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "dv_qenc_time_layers": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float)]),
+    "dv_qenc_probe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "dv_op_rel_attention": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_regulate_lengths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_op_regulate_sample": (C.c_int, [C.c_void_p] * 5 + [C.c_double] + [C.c_int32] * 4 + [C.c_void_p] * 4),

@@ -325,6 +325,36 @@ struct RelAttnParams {
 };
 hipError_t launch_rel_attention(const RelAttnParams& p, hipStream_t st);
 
+// One WaveNet layer of the posterior encoder as ONE launch (k_wn_layer, kernels_wn.hip; reference modules.py:133-210): the
+// five-tap gated convolution, the gate, the 1x1 res/skip convolution and both updates.  Rows m = b * T + t, 64-row tiles of one
+// utterance.  x_in / x_out must be different buffers (neighbouring tiles read x_in as their halo); skip_in may be skip_out.
+struct WnLayerParams {
+  const float* x_in; const bf16_t* xh_in; const bf16_t* xl_in;      // the layer's input [B * T, H]: fp32 and split planes
+  float* x_out; bf16_t* xh_out; bf16_t* xl_out;                     // (x + rs[:, :H]) * keep (not written by the last layer)
+  const float* skip_in; float* skip_out;                            // running skip sum [B * T, H] (first layer: skip_in is not read)
+  bf16_t* sh_out; bf16_t* sl_out;                                   // last layer: split planes of the finished skip sum
+  const bf16_t* w1_hi; const bf16_t* w1_lo;                         // in_layer, fragment-major [2H / 32][5H / 16], rows in GEGLU order
+  const float* b1;                                                  // [2H], the reference's order
+  const float* cond; int ld_cond, cond_off;                         // conditioning [B, ld_cond], this layer's slice at cond_off; null: none
+  const bf16_t* w2_hi; const bf16_t* w2_lo;                         // res_skip_layer, fragment-major [2H / 32 (last: H / 32)][H / 16]
+  const float* b2;                                                  // [2H] (last: [H])
+  const int64_t* lengths;                                           // [B] device; clamped to 0 .. T
+  float* acts_out;                                                  // gated activations [B * T, H] for the probe, or null
+  int B, T, tiles_per_utt;                                          // tiles_per_utt = ceil(T / 64)
+  int first, last;
+};
+bool wn_layer_supported(int H);
+hipError_t wn_init();     // one-time kernel attribute setup (call outside stream capture)
+hipError_t launch_wn_layer(const WnLayerParams& p, int H, hipStream_t st);
+// mel [B, Cin, T] -> planes [B * T, Kp] + keep [B * T]; with g: cond[B, Nc] = g[B, gin] Wc[Nc, gin]^T + bc in the same launch
+hipError_t launch_wn_pack(const float* y, const int64_t* lengths, bf16_t* hi, bf16_t* lo, float* keep, int B, int Cin, int T, int Kp,
+                          const float* g, const float* Wc, const float* bc, float* cond, int gin, int Nc, hipStream_t st);
+// z [B * T, 2C] (m | logs) -> zo = (m + noise * expf(logs)) * keep, m, logs, all [B, C, T]
+hipError_t launch_wn_store(const float* z, const float* noise, const int64_t* lengths, float* zo, float* m_out, float* logs_out, int B, int T,
+                           int C, hipStream_t st);
+// weight norm: w[n, :] = v[n, :] * (g[n] / ||v[n, :]||)
+hipError_t launch_wn_fold(const float* v, const float* g, float* w, int N, int per_row, hipStream_t st);
+
 // ---------------------------------------------------------------------------------------
 // Persistent per-XCD schedule (persist.hip): operation table in device memory, executed by one launch.
 // ---------------------------------------------------------------------------------------

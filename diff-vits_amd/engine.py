@@ -891,6 +891,106 @@ class TextEncoderEngine:
         return out
 
 
+class PosteriorEncoderEngine:
+    """Native posterior encoder `enc_q` (dv_qenc_*, include/dvits_hip.h) for one mirror module
+    (diff_vits_amd.model3.PosteriorEncoder): one k_wn_layer launch per WaveNet layer (csrc/kernels_wn.hip).  Weights are synced
+    like TextEncoderEngine's (re-packed, weight norm folded, when a parameter's data_ptr / _version moves); the planned schedule
+    is kept per (B, T): the handle holds one, a change of shape re-plans it (the packed weights survive)."""
+
+    def __init__(self, module):
+        self.module = module
+        wn = module.enc
+        c = _lib.QencCfg()
+        c.in_channels, c.out_channels, c.hidden_channels = module.pre.in_channels, module.out_channels, wn.hidden_channels
+        c.kernel_size, c.n_layers, c.gin_channels = wn.in_layers[0].kernel_size[0], wn.n_layers, wn.gin_channels
+        c.dilation_rate = wn.in_layers[1].dilation[0] if wn.n_layers > 1 else 1
+        self.cfg = c
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().dv_qenc_create(C.byref(c), C.byref(self._h)), "dv_qenc_create")
+        self._weight_sig = None
+        self._prepared = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                _lib.lib().dv_qenc_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def sync_weights(self):
+        m = self.module
+        sig = tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
+        if sig == self._weight_sig:
+            return
+        L = _lib.lib()
+        for name, t in m.state_dict().items():
+            if not t.is_cuda:
+                raise RuntimeError("backend='hip' needs the module on a GPU (parameter %s is on %s)" % (name, t.device))
+            t32 = t.detach().to(torch.float32).contiguous()
+            shape = (C.c_int64 * t32.dim())(*t32.shape)
+            _lib.check(L.dv_qenc_set_weight(self._h, name.encode(), _lib.ptr(t32), shape, t32.dim()), "dv_qenc_set_weight(%s)" % name)
+        torch.cuda.synchronize()
+        self._weight_sig = sig
+        self._prepared = None
+
+    def forward(self, y, lengths, g=None, noise=None):
+        """y float [B, Cin, T], lengths int64 [B], g [B, gin] / [B, gin, 1] or None, noise [B, C, T] or None (drawn here with
+        torch.randn on y's device), all on the GPU -> (z, m, logs) float32 [B, C, T], padding frames zero.  Nothing here reads
+        the device: the call can be captured into a graph once the shape is prepared."""
+        for name, t in (("y", y), ("y_lengths", lengths)) + ((("g", g),) if g is not None else ()) + ((("noise", noise),) if noise is not None else ()):
+            if not t.is_cuda:
+                raise RuntimeError("posterior encoder backend='hip' needs GPU tensors; got %s on %s" % (name, t.device))
+        c = self.cfg
+        if y.dim() != 3 or y.shape[1] != c.in_channels:
+            raise ValueError("y must be [B, %d, T], got shape %s" % (c.in_channels, tuple(y.shape)))
+        B, _, T = y.shape
+        if lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,):
+            raise ValueError("y_lengths must be int64 of shape (%d,), got %s %s" % (B, lengths.dtype, tuple(lengths.shape)))
+        self.sync_weights()
+        if (B, T) != self._prepared:
+            _lib.check(_lib.lib().dv_qenc_prepare(self._h, B, T, _lib.PREC_BF16X3), "dv_qenc_prepare")
+            self._prepared = (B, T)
+        gp = None
+        if g is not None:
+            if c.gin_channels == 0:
+                raise ValueError("this posterior encoder was built without speaker conditioning (gin_channels = 0)")
+            gp = g.detach().to(torch.float32).reshape(B, -1).contiguous()
+            if gp.shape[1] != c.gin_channels:
+                raise ValueError("g must hold %d channels per utterance, got %s" % (c.gin_channels, tuple(g.shape)))
+        if noise is None:
+            eps = torch.randn((B, c.out_channels, T), device=y.device, dtype=torch.float32)
+        else:
+            if tuple(noise.shape) != (B, c.out_channels, T):
+                raise ValueError("noise must be %s, got %s" % ((B, c.out_channels, T), tuple(noise.shape)))
+            eps = noise.detach().to(torch.float32).contiguous()
+        y32 = y.detach().to(torch.float32).contiguous()
+        lengths = lengths.contiguous()
+        out = torch.empty((3, B, c.out_channels, T), device=y.device, dtype=torch.float32)
+        _lib.check(_lib.lib().dv_qenc_forward(self._h, _lib.ptr(y32), _lib.ptr(lengths), _lib.ptr(gp), _lib.ptr(eps), _lib.ptr(out[0]),
+                                              _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream_ptr()), "dv_qenc_forward")
+        return out[0], out[1], out[2]
+
+    def stats(self):
+        n, f = C.c_int64(), C.c_double()
+        _lib.check(_lib.lib().dv_qenc_stats(self._h, C.byref(n), C.byref(f)), "dv_qenc_stats")
+        return n.value, f.value
+
+    def time_layers(self, reps=50):
+        """Microseconds per pass of the n_layers k_wn_layer launches of the last forward, replayed `reps` times between two events."""
+        us = C.c_float()
+        _lib.check(_lib.lib().dv_qenc_time_layers(self._h, reps, _lib.stream_ptr(), C.byref(us)), "dv_qenc_time_layers")
+        return us.value
+
+    def probe(self, name):
+        """Named intermediate [B, T, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1 at prepare time)."""
+        dims = (C.c_int64 * 3)()
+        _lib.check(_lib.lib().dv_qenc_probe(self._h, name.encode(), None, 0, dims), "dv_qenc_probe")
+        out = torch.empty(tuple(dims), dtype=torch.float32)
+        _lib.check(_lib.lib().dv_qenc_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims), "dv_qenc_probe")
+        return out
+
+
 def check_index_tensor(name, t, n, shape):
     """int64, the expected shape, every entry in [0, n): ValueError otherwise (works on CPU and GPU tensors)."""
     if t.dtype != torch.int64:

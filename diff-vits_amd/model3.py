@@ -787,16 +787,44 @@ class WN(nn.Module):
 class PosteriorEncoder(nn.Module):
     """reference model3.PosteriorEncoder (model3.py:526-572): mel frames -> the posterior's statistics and one draw from it,
     (z, m, logs, mask).  `noise=` [B, out_channels, T] fixes the draw (None: torch.randn_like, as the reference).  Sixteen
-    WaveNet layers of torch ops on the tensor's device: the forced aligner's only user runs it once per recording."""
+    WaveNet layers of torch ops on the tensor's device by default; backend='hip' (opt-in) runs the whole forward on the native
+    posterior-encoder engine (dv_qenc_*, csrc/qenc.hip: one launch per WaveNet layer) and fails loudly where it cannot."""
 
-    def __init__(self, in_channels, out_channels, hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=0):
+    def __init__(self, in_channels, out_channels, hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=0,
+                 backend=None):
         super().__init__()
+        if backend not in (None, "hip"):
+            raise ValueError("backend must be None or 'hip', got %r" % (backend,))
+        self.backend = backend                 # None: the torch ops below; 'hip': the dv_qenc engine (opt-in)
+        self._engine = None
+        self.native_calls = 0                  # how often the native engine ran
         self.out_channels = out_channels
         self.pre = nn.Conv1d(in_channels, hidden_channels, 1)
         self.enc = WN(hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=gin_channels)
         self.proj = nn.Conv1d(hidden_channels, out_channels * 2, 1)
 
+    def hip_engine(self):
+        if self._engine is None:
+            from .engine import PosteriorEncoderEngine
+            self._engine = PosteriorEncoderEngine(self)
+        return self._engine
+
+    def _forward_hip(self, x, x_lengths, g, noise):
+        """The native path: GPU tensors or a RuntimeError naming the CPU one - never a fall-back to the torch ops.  noise=None
+        draws torch.randn on the device here and hands it in."""
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("backend='hip' is inference-only; construct with backend=None to train")
+        for name, t in (("x", x), ("x_lengths", x_lengths), ("g", g), ("noise", noise)):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("posterior encoder backend='hip' needs GPU tensors; got %s on %s" % (name, t.device))
+        z, m, logs = self.hip_engine().forward(x, x_lengths.to(torch.int64), g, noise)
+        self.native_calls += 1
+        x_mask = torch.unsqueeze(sequence_mask(x_lengths, x.size(2)), 1).to(z.dtype)
+        return z, m, logs, x_mask
+
     def forward(self, x, x_lengths, g=None, noise=None):
+        if self.backend == "hip":
+            return self._forward_hip(x, x_lengths, g, noise)
         x_mask = torch.unsqueeze(sequence_mask(x_lengths, x.size(2)), 1).to(x.dtype)
         h = self.enc(self.pre(x) * x_mask, x_mask, g=g)
         m, logs = torch.split(self.proj(h) * x_mask, self.out_channels, dim=1)
@@ -910,13 +938,17 @@ class VITS(nn.Module):
     the resolved integer durations to the return value.  With aligner=True the posterior encoder `enc_q` (reference names) is
     built and `align` gives the frames of a recording to the tokens of its transcript (the reference's training-time monotonic
     alignment search, model3.py:755-798): torch ops and a host search by default, align_backend='hip' for the two native
-    operators dv_op_mas_scores / dv_op_mas_path (csrc/kernels_align.hip; GPU tensors only, never a fall-back)."""
+    operators dv_op_mas_scores / dv_op_mas_path (csrc/kernels_align.hip; GPU tensors only, never a fall-back), and
+    posterior_backend='hip' (opt-in) for enc_q on the native posterior-encoder engine (`native_posterior_calls` counts its runs)."""
 
     def __init__(self, n_vocab=None, spec_channels=None, inter_channels=128, hidden_channels=256, filter_channels=256,
                  n_heads=2, n_layers=6, kernel_size=3, p_dropout=0.1, gin_channels=256, enc_p=None, n_tones=11, n_languages=3,
-                 backend=None, text_encoder_backend=None, prior_backend=None, aligner=False, **unused):
+                 backend=None, text_encoder_backend=None, prior_backend=None, aligner=False, posterior_backend=None, **unused):
         super().__init__()
         from .unet1d.embeddings import TextTimeEmbedding
+        if posterior_backend not in (None, "hip"):
+            raise ValueError("posterior_backend must be None or 'hip', got %r" % (posterior_backend,))
+        self.posterior_backend = posterior_backend   # None: enc_q's torch ops; 'hip': the dv_qenc engine (opt-in, with aligner=True)
         if prior_backend not in (None, "hip"):
             raise ValueError("prior_backend must be None or 'hip', got %r" % (prior_backend,))
         self.prior_backend = prior_backend     # None: the torch ops of infer_from_encoder; 'hip': dv_op_regulate_* (opt-in)
@@ -924,7 +956,7 @@ class VITS(nn.Module):
         self.native_align_calls = 0            # how often the native aligner (scores + search) ran
         self.inter_channels, self.hidden_channels, self.gin_channels = inter_channels, hidden_channels, gin_channels
         if aligner:
-            self.enc_q = PosteriorEncoder(100, inter_channels, hidden_channels, 5, 1, 16, gin_channels)
+            self.enc_q = PosteriorEncoder(100, inter_channels, hidden_channels, 5, 1, 16, gin_channels, backend=posterior_backend)
         if enc_p is not None:
             self.enc_p = enc_p
         elif n_vocab is not None:
@@ -934,6 +966,11 @@ class VITS(nn.Module):
         self.ref_enc = TextTimeEmbedding(100, gin_channels, 1)
         self.o_proj = PromptEncoder(inter_channels, hidden_channels, inter_channels, 6, 0.2, gin_channels=gin_channels,
                                     backend=backend)
+
+    @property
+    def native_posterior_calls(self):
+        """How often the native posterior encoder ran (0 without aligner=True / posterior_backend='hip')."""
+        return self.enc_q.native_calls if hasattr(self, "enc_q") else 0
 
     @torch.no_grad()
     def infer_from_encoder(self, x, m_p, logs_p, x_mask, x_lengths, y, y_lengths, g=None, noise_scale=0.667, length_scale=1,

@@ -23,11 +23,12 @@ from .model3 import VITS, NaturalSpeech2
 TRAINING_ONLY_PREFIXES = ("vits.enc_q.",)
 
 
-def build_model(cfg, n_vocab, backend=None, text_encoder_backend=None, prior_backend=None, aligner=False):
+def build_model(cfg, n_vocab, backend=None, text_encoder_backend=None, prior_backend=None, aligner=False, posterior_backend=None):
     """NaturalSpeech2(cfg) as model3.py:955-975 builds it: VITS(len(symbols), window_size // 2 + 1, **cfg['vits']).
-    aligner=True: with the posterior encoder `vits.enc_q` (VITS.align), whose checkpoint entries load_state then loads."""
+    aligner=True: with the posterior encoder `vits.enc_q` (VITS.align), whose checkpoint entries load_state then loads;
+    posterior_backend='hip' (opt-in) runs it on the native posterior-encoder engine."""
     vits = VITS(n_vocab, cfg["data"]["window_size"] // 2 + 1, backend=backend, text_encoder_backend=text_encoder_backend,
-                prior_backend=prior_backend, aligner=aligner, **cfg["vits"])
+                prior_backend=prior_backend, aligner=aligner, posterior_backend=posterior_backend, **cfg["vits"])
     return NaturalSpeech2(cfg, vits=vits, backend=backend)
 
 
@@ -45,7 +46,7 @@ def load_state(model, state_dict):
     return skipped
 
 
-def load_model(model_path, device, cfg, n_vocab=None, backend=None, aligner=False):
+def load_model(model_path, device, cfg, n_vocab=None, backend=None, aligner=False, posterior_backend=None):
     """tts_infer.py:76-81: torch.load -> NaturalSpeech2(cfg) -> load_state_dict(data['model']) -> .to(device).eval()."""
     data = torch.load(model_path, map_location="cpu", weights_only=True)
     if not isinstance(data, dict) or "model" not in data:
@@ -55,7 +56,7 @@ def load_model(model_path, device, cfg, n_vocab=None, backend=None, aligner=Fals
         if "vits.enc_p.emb.weight" not in sd:
             raise ValueError("checkpoint has no vits.enc_p.emb.weight; pass n_vocab")
         n_vocab = sd["vits.enc_p.emb.weight"].shape[0]
-    model = build_model(cfg, n_vocab, backend=backend, aligner=aligner)
+    model = build_model(cfg, n_vocab, backend=backend, aligner=aligner, posterior_backend=posterior_backend)
     load_state(model, sd)
     return model.to(device).eval()
 

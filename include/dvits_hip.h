@@ -87,10 +87,23 @@ typedef struct {
   int32_t cond_layer_idx;         /* the layer in front of which the speaker vector is added */
 } dv_tenc_cfg;
 
+/* PosteriorEncoder constructor arguments (reference model3.py:526-548 over modules.WN): the product is 100 mel channels -> 256
+ * hidden channels, 16 layers of 5-tap gated convolutions with dilation 1, 128 output channels, a 256-wide speaker vector. */
+typedef struct {
+  int32_t in_channels;            /* mel channels (any; the input planes are padded to a multiple of 64) */
+  int32_t out_channels;           /* C: proj writes 2C statistics channels (m | logs); a multiple of 16 */
+  int32_t hidden_channels;        /* H: k_wn_layer is instantiated for 256 */
+  int32_t kernel_size;            /* 5 */
+  int32_t dilation_rate;          /* 1 */
+  int32_t n_layers;
+  int32_t gin_channels;           /* speaker vector width, 0 = no cond_layer */
+} dv_qenc_cfg;
+
 typedef struct dv_unet dv_unet;
 typedef struct dv_plan dv_plan;
 typedef struct dv_penc dv_penc;
 typedef struct dv_tenc dv_tenc;
+typedef struct dv_qenc dv_qenc;
 typedef struct dv_voice dv_voice;
 
 const char* dv_last_error(void);
@@ -415,6 +428,37 @@ int dv_tenc_stats(dv_tenc* t, int64_t* n_launch, double* flops);
  * "layerN.attn" (after conv_o + residual, before LayerNorm 1), "layerN.ln1", "layerN.ffn1" (ReLU'd, masked conv_1 output, joined
  * from its split planes), "layerN" (the layer's output), "proj" (2C statistics channels).  Padding rows hold zeros. */
 int dv_tenc_probe(dv_tenc* t, const char* name, float* host_out, int64_t capacity, int64_t* dims);
+
+/* ---- posterior encoder enc_q: PosteriorEncoder.forward, reference model3.py:550-572 (mel frames -> posterior draw) -------
+ * The contracts of the dv_tenc_* functions.  Weights under their reference names relative to "enc_q.": "pre.{weight,bias}",
+ * "enc.in_layers.N.{weight_g,weight_v,bias}", "enc.res_skip_layers.N.{weight_g,weight_v,bias}", "enc.cond_layer.{weight_g,weight_v,bias}",
+ * "proj.{weight,bias}"; float32, in the reference's shapes, copied.  Weight norm (w = weight_g * weight_v / ||weight_v||, the norm
+ * per output channel) is folded when the weights are packed. */
+int dv_qenc_create(const dv_qenc_cfg* cfg, dv_qenc** out);
+void dv_qenc_destroy(dv_qenc* q);
+int dv_qenc_set_weight(dv_qenc* q, const char* name, const void* dev_ptr, const int64_t* shape, int32_t ndim);
+/* Packs the weights (once per weight set) and plans the launches for B utterances of T frames.  DV_ERR_INVALID with a message,
+ * before anything is launched, for what k_wn_layer (csrc/kernels_wn.hip) does not cover: kernel_size != 5, dilation_rate != 1,
+ * hidden_channels != 256, DV_PREC_BF16, T > 16384 (the aligner's limit), B > 65535, B * T > 2^22. */
+int dv_qenc_prepare(dv_qenc* q, int32_t B, int32_t T, int32_t precision);
+/* y: DEVICE float32 [B, in_channels, T]; lengths: DEVICE int64 [B], valid frames per utterance (values outside 0..T are clamped;
+ * a zero-length utterance yields zeros and leaves the others alone); g: [B, gin_channels] float32 or NULL (no speaker
+ * conditioning in this call); noise: [B, C, T] float32, the posterior draw.  Outputs channels-first [B, C, T], padding frames
+ * exactly zero: z = (m + noise * exp(logs)) * mask, m, logs.  n_layers + 4 launches.  Allocates nothing and never waits for the
+ * device: capturable into a graph. */
+int dv_qenc_forward(dv_qenc* q, const float* y, const int64_t* lengths, const float* g, const float* noise, float* z, float* m,
+                    float* logs, void* stream);
+/* Launches one forward enqueues (n_layers + 4, in either mode) and the FLOPs of its contractions. */
+int dv_qenc_stats(dv_qenc* q, int64_t* n_launch, double* flops);
+/* Measurement aid (tools/qenc_bench.py): replays the n_layers k_wn_layer launches of the last dv_qenc_forward (its buffers and
+ * arguments; DV_ERR_STATE without one) `reps` times between two events on `stream`, waits, and returns microseconds per pass of
+ * n_layers launches.  lengths (and g) of that forward must still be alive.  The schedule's activations are overwritten with the values the same layers would write again. */
+int dv_qenc_time_layers(dv_qenc* q, int32_t reps, void* stream, float* us_per_pass);
+/* Probe, the contract of dv_tenc_probe (channels-last [B, T, C], after a prepare with DVITS_KEEP_INTERMEDIATES=1).  Names: "pre",
+ * "layerN.acts" (the gated activations tanh * sigmoid, which only this mode writes to memory), "layerN.x" (the residual stream
+ * after layer N; not for the last layer, which has no residual half), "layerN.skip" (the running skip sum), "proj" (2C statistics
+ * channels).  Padding rows hold zeros. */
+int dv_qenc_probe(dv_qenc* q, const char* name, float* host_out, int64_t capacity, int64_t* dims);
 
 /* ---- single-operator entry points (parity tests of each kernel through the C ABI) ---- */
 
