@@ -41,6 +41,10 @@ class QencCfg(C.Structure):
                                          "gin_channels")]
 
 
+class MelCfg(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("n_mels", C.c_int32), ("center", C.c_int32), ("log_clip", C.c_float)]
+
+
 MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p)
 
 # every symbol include/dvits_hip.h declares: (restype, argtypes)
@@ -87,6 +91,10 @@ SIGNATURES = {
     "dv_qenc_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "dv_qenc_time_layers": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_float)]),
     "dv_qenc_probe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "dv_mel_create": (C.c_int, [C.POINTER(MelCfg), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "dv_mel_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_void_p]),
+    "dv_mel_destroy": (None, [C.c_void_p]),
     "dv_op_rel_attention": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_regulate_lengths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_op_regulate_sample": (C.c_int, [C.c_void_p] * 5 + [C.c_double] + [C.c_int32] * 4 + [C.c_void_p] * 4),
@@ -144,6 +152,7 @@ SIGNATURES = {
 }
 LN_STATS, LN_ROWS, LN_APPLY, LN_AFFINE = 0, 1, 2, 3
 GN_STAT16, GN_SLAB, GN_KSTAT16 = 0, 1, 2
+MEL_LOG, MEL_POWER2 = 1, 2
 # k_gemm's tile menu (DV_GT_*), epilogues (DV_GEMM_*) and the fused split-K flag of dv_op_gemm
 GT = {"auto": 0, "T0": 1, "T1": 2, "T2": 3, "T2S": 4, "T2G": 5, "T3": 6, "T4": 7, "T4G": 8, "T0S": 9}
 GT_BK64 = 0x100

@@ -6,7 +6,7 @@ What stays the reference's own: the text front-end (`text/`: G2P, cleaners, the 
 both are outside the diffusion hot path and their third-party dependencies are absent from this image.  So:
   * the size of the symbol table is taken from the checkpoint (`vits.enc_p.emb.weight`) unless `n_vocab` is passed;
   * `synthesize` takes batches whose reference audio is either a waveform tensor at 24 kHz (mel front-end of mel.py,
-    parity unpinned there) or a ready log-mel prompt `[1, 100, L]`; a PATH needs torchaudio for decoding / resampling,
+    pinned there to the fp64 restatement of its documented definition) or a ready log-mel prompt `[1, 100, L]`; a PATH needs torchaudio for decoding / resampling,
     exactly as in the reference, and raises ImportError when it is missing.
 Training-only checkpoint entries (the posterior encoder `vits.enc_q.*`) are not
 part of the inference model and are skipped when loading; every key the inference model owns must be present.
@@ -66,9 +66,9 @@ def save_checkpoint(model, step, path):
     torch.save({"step": int(step), "model": model.state_dict()}, str(path))
 
 
-def refer_prompt(refer, device):
+def refer_prompt(refer, device, mel_backend=None):
     """Reference audio -> log-mel prompt [1, 100, L] (tts_infer.py:54-67).  `refer`: path, waveform [1, n] at 24 kHz,
-    or an already computed log-mel [1, 100, L]."""
+    or an already computed log-mel [1, 100, L].  mel_backend='hip' (opt-in): the native front-end (mel.py), one launch."""
     if isinstance(refer, (str, bytes)) or hasattr(refer, "__fspath__"):
         try:
             import torchaudio
@@ -83,14 +83,26 @@ def refer_prompt(refer, device):
         return refer.to(device=device, dtype=torch.float32)
     if refer.dim() != 2:
         raise ValueError("reference audio must be [channels, samples] or a log-mel [1, 100, L], got %s" % (tuple(refer.shape),))
-    return reference_mel_prompt(refer.to(device=device, dtype=torch.float32))
+    return reference_mel_prompt(refer.to(device=device, dtype=torch.float32), backend=mel_backend)
 
 
-def synthesize(model, cfg, vocos, batchs, control_values=None, device="cuda", prompt_length="reference", **sample_kw):
+def recording_mels(waves, n_samples, device, mel_backend=None):
+    """A batch of recordings -> (y, y_lengths) for `VITS.align(..., y, y_lengths, ...)` and `NaturalSpeech2.enroll_voice`:
+    waves [B, n_max] at 24 kHz (zero padded, or any content behind each row's samples), n_samples [B] -> the log-mel
+    y [B, 100, 1 + n_max // 256] with zeros behind every row's own frames, and y_lengths int64 [B] = 1 + n_samples // 256.
+    Every row is the mel of its own recording alone (reflect padding about its own end), on either backend;
+    mel_backend='hip' computes the batch in one launch."""
+    waves = torch.as_tensor(waves).to(device=device, dtype=torch.float32)
+    n_samples = torch.as_tensor(n_samples).to(device=device, dtype=torch.int64)
+    return reference_mel_prompt(waves, lengths=n_samples, backend=mel_backend)
+
+
+def synthesize(model, cfg, vocos, batchs, control_values=None, device="cuda", prompt_length="reference", mel_backend=None,
+               **sample_kw):
     """tts_infer.py:46-75 with the same batch tuples `(phoneme, tone, language, refer, phoneme_length)`; returns the last
     batch's samples like the reference (and its mel as a second value).  `control_values` is accepted and, as in the
     reference, unused.  Extra keywords (`sample_method`, `noise`, `prior_noise`, `known_mel` / `known_mask` / `known_noise` /
-    `paste_known` for infilling, ...) go to `model.sample`.
+    `paste_known` for infilling, ...) go to `model.sample`; `mel_backend` goes to `refer_prompt`.
 
     prompt_length: tts_infer.py:68 passes `refer.size(1)` - the mel CHANNEL count, 100 - as the prompt length, so the
     prompt masks cover the first 100 frames whatever the audio's length.  "reference" keeps that; "frames" passes the
@@ -111,7 +123,7 @@ def synthesize(model, cfg, vocos, batchs, control_values=None, device="cuda", pr
             spec, refer_length = refer.refer.to(device), refer.refer_length.to(device)
             kw = dict(sample_kw, voices=[refer])
         else:
-            spec = refer_prompt(refer, device)
+            spec = refer_prompt(refer, device, mel_backend=mel_backend)
             refer_length = torch.tensor([spec.size(1) if prompt_length == "reference" else spec.size(2)]).to(device)
             kw = sample_kw
         with torch.no_grad():

@@ -99,12 +99,23 @@ typedef struct {
   int32_t gin_channels;           /* speaker vector width, 0 = no cond_layer */
 } dv_qenc_cfg;
 
+/* Log-mel front-end (mel.py MelSpectrogram as tts_infer.py:57-66 builds it).  Built: n_fft 1024, hop_length 256, centred frames
+ * with reflect padding, one-sided spectrum, n_mels <= 128; everything else is refused at create. */
+typedef struct {
+  int32_t n_fft;                  /* 1024 */
+  int32_t hop_length;             /* 256 */
+  int32_t n_mels;                 /* 1..128 (100) */
+  int32_t center;                 /* 1 */
+  float   log_clip;               /* floor under the logarithm of DV_MEL_LOG, > 0 (1e-7) */
+} dv_mel_cfg;
+
 typedef struct dv_unet dv_unet;
 typedef struct dv_plan dv_plan;
 typedef struct dv_penc dv_penc;
 typedef struct dv_tenc dv_tenc;
 typedef struct dv_qenc dv_qenc;
 typedef struct dv_voice dv_voice;
+typedef struct dv_mel dv_mel;
 
 const char* dv_last_error(void);
 /* Library/version probe: returns e.g. "dvits_hip 0.1 gfx950". */
@@ -459,6 +470,27 @@ int dv_qenc_time_layers(dv_qenc* q, int32_t reps, void* stream, float* us_per_pa
  * after layer N; not for the last layer, which has no residual half), "layerN.skip" (the running skip sum), "proj" (2C statistics
  * channels).  Padding rows hold zeros. */
 int dv_qenc_probe(dv_qenc* q, const char* name, float* host_out, int64_t capacity, int64_t* dims);
+
+/* ---- log-mel front-end: a ragged batch of recordings -> mels in one launch (csrc/kernels_mel.hip) ---- */
+
+/* window: HOST float32 [n_fft], fb: HOST float32 [n_fft / 2 + 1, n_mels] (row = bin) - the buffers mel.MelSpectrogram registers, so
+ * both of its backends share the constants bit for bit.  They are copied to device tables together with the FFT twiddles (computed
+ * in double on the host, rounded once) and each band's bin range (first and last non-zero row of its fb column; the dense weights
+ * inside the range are used, so any filterbank is handled).  A configuration outside dv_mel_cfg's scope, a non-finite table entry:
+ * DV_ERR_INVALID with the reason in dv_last_error. */
+int dv_mel_create(const dv_mel_cfg* cfg, const float* window, const float* fb, dv_mel** out);
+typedef enum { DV_MEL_LOG = 1, DV_MEL_POWER2 = 2 } dv_mel_flags;
+/* k_log_mel: wave float32 [B, n_max], n_samples DEVICE int64 [B] -> out float32 [B, n_mels, L_max], frames DEVICE int64 [B].
+ * L_max must be 1 + n_max / hop_length; frames[b] = L_b = 1 + n_samples[b] / hop_length.  Frame f of row b is the windowed samples
+ * f * hop - n_fft / 2 + j, j < n_fft, reflected about the ROW's own ends (i < 0 -> -i, i >= n_b -> 2 (n_b - 1) - i; no sample at an
+ * index >= n_b is read), a 1024-point real DFT in float32, the 513 magnitudes (sqrtf; squared with DV_MEL_POWER2), per mel band the
+ * sum of fb[k, m] * mag[k] over the band's bin range in ascending k, and with DV_MEL_LOG logf(fmaxf(v, log_clip)).  Every element at
+ * or past L_b is exactly 0.  A row whose n_samples[b] is outside [n_fft / 2 + 1, n_max] is all zeros with frames[b] = 0: a value for
+ * the caller to check, not a fault.  Null pointers, B outside 1..65535, n_max outside n_fft / 2 + 1 .. 2^30, a wrong L_max, unknown
+ * flag bits, misaligned pointers: DV_ERR_INVALID before anything is launched.  One launch, no allocation, no wait: capturable. */
+int dv_mel_forward(dv_mel* h, const float* wave, const int64_t* n_samples, int32_t B, int32_t n_max, float* out, int64_t* frames,
+                   int32_t L_max, int32_t flags, void* stream);
+void dv_mel_destroy(dv_mel* h);
 
 /* ---- single-operator entry points (parity tests of each kernel through the C ABI) ---- */
 
