@@ -5,8 +5,7 @@
 // Appendix A gives the block order; reference unet1d/unet_1d_condition.py:743-1037).
 // Step-invariant work (pooled-text embedding, the cross-attention K/V projections, the
 // mask bias) is a second schedule run by dv_unet_set_cond().
-#include "../../include/dvits_hip.h"
-#include "dv_common.h"
+#include "engine_core.h"
 
 #include <algorithm>
 #include <atomic>
@@ -43,15 +42,6 @@ extern "C" const char* dv_version(void) { return "dvits_hip 0.3 gfx950 src=" DV_
 // generation), and a destroyed handle's address can be handed out again by `new` - with a per-handle counter the new
 // handle's first prepare would reproduce the old key and replay a graph that points into freed memory.
 static std::atomic<int64_t> g_generation{0};
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return dv_fail(DV_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
 // ----------------------------------------------------------------------------- arena
 // Plan-time allocator over one device slab: the schedule is static and stream-ordered, so a
@@ -131,8 +121,6 @@ struct Arena {
 };
 
 // ----------------------------------------------------------------------------- data
-struct RawW { float* p = nullptr; std::vector<int64_t> shape; size_t numel = 0; };
-
 struct PackedW {
   bf16_t* hi = nullptr; bf16_t* lo = nullptr; float* bias = nullptr;
   bf16_t* fhi = nullptr; bf16_t* flo = nullptr;   // fragment-major copies for the row-block chains (made on demand)
@@ -155,8 +143,6 @@ struct Act {   // channels-last fp32 [B*Tp, C] (+ GN statistics) (+ split planes
   bf16_t* sn_hi = nullptr; bf16_t* sn_lo = nullptr; bf16_t* sr_hi = nullptr; bf16_t* sr_lo = nullptr;
 };
 
-typedef std::function<hipError_t(hipStream_t)> OpFn;
-
 // p: fp32 rows, Tp frames per utterance apart.  Split-plane tensors (p null): hi (+ lo, bf16x3) planes, joined on the host and
 // multiplied by `scale` (a factor the schedule folds into the consumer's weights).  A tap (DVITS_KEEP_INTERMEDIATES=tap) has the same
 // form: its pointers are side buffers outside the arena, filled by a copy operation of the schedule
@@ -165,7 +151,7 @@ struct Probe { std::string name; float* p; int T, C, Tp; const bf16_t* hi = null
 struct dv_unet {
   dv_unet_cfg cfg{};
   dv_penc_cfg pcfg{};                        // prompt-encoder handles (dv_penc wraps a dv_unet core)
-  std::map<std::string, RawW> w;
+  WeightStore w;
   bool weights_dirty = true;
   // prepared state
   bool prepared = false, cond_set = false;
@@ -293,27 +279,16 @@ extern "C" void dv_unet_destroy(dv_unet* u) {
   (void)hipDeviceSynchronize();
   unet_release_prepared(u);
   if (u->gnx_status) (void)hipHostFree(u->gnx_status);
-  for (auto& kv : u->w)
-    if (kv.second.p) (void)hipFree(kv.second.p);
+  u->w.free_all();
   delete u;
 }
 
+// (a new weight marks the packed weights stale; the schedule itself is dropped by the next prepare, not here)
 extern "C" int dv_unet_set_weight(dv_unet* u, const char* name, const void* dev_ptr, const int64_t* shape, int32_t ndim) {
-  if (!u || !name || !dev_ptr || !shape || ndim < 1 || ndim > 4) return dv_fail(DV_ERR_INVALID, "dv_unet_set_weight: bad argument");
-  size_t n = 1;
-  std::vector<int64_t> sh(shape, shape + ndim);
-  for (auto s : sh) n *= (size_t)s;
-  RawW& r = u->w[name];
-  if (r.numel != n) {
-    if (r.p) (void)hipFree(r.p);
-    r.p = nullptr;
-    HIPCHK(hipMalloc((void**)&r.p, n * sizeof(float)));
-  }
-  r.shape = sh;
-  r.numel = n;
-  HIPCHK(hipMemcpy(r.p, dev_ptr, n * sizeof(float), hipMemcpyDeviceToDevice));
-  u->weights_dirty = true;
-  return DV_OK;
+  if (!u) return dv_fail(DV_ERR_INVALID, "dv_unet_set_weight: bad argument");
+  int rc = u->w.set(name, dev_ptr, shape, ndim, "dv_unet_set_weight");
+  if (rc == DV_OK) u->weights_dirty = true;
+  return rc;
 }
 
 // ----------------------------------------------------------------------------- plan builder
@@ -398,12 +373,13 @@ struct Builder {
 
   // ---- weights
   const RawW* raw(const std::string& name) {
-    auto it = u->w.find(name);
-    if (it == u->w.end()) { if (err.empty()) err = "missing weight: " + name; return nullptr; }
-    return &it->second;
+    PlanError pe;
+    const RawW* r = u->w.find(name, WeightStore::ANY_NUMEL, pe);
+    if (!r && err.empty()) err = pe.msg;
+    return r;
   }
   const float* W(const std::string& name) { const RawW* r = raw(name); return r ? r->p : nullptr; }
-  bool has(const std::string& name) { return u->w.count(name) != 0; }
+  bool has(const std::string& name) { return u->w.recs.count(name) != 0; }
 
   // ---- arena
   float* alloc(size_t floats) {
@@ -1994,7 +1970,7 @@ struct Builder {
     if (dry) return nullptr;
     size_t n = 1;
     for (auto v : shape) n *= (size_t)v;
-    RawW& r = u->w[name];
+    RawW& r = u->w.recs[name];
     if (r.numel != n) {
       if (r.p) (void)hipFree(r.p);
       r.p = nullptr;
@@ -2006,12 +1982,12 @@ struct Builder {
 
   // engine-made constant vector registered like a weight (per-source-channel scale for pack())
   void const_vec(const std::string& name, int n, float value) {
-    if (dry || u->w.count(name)) return;
+    if (dry || has(name)) return;
     RawW r;
     if (hipMalloc((void**)&r.p, (size_t)n * 4) != hipSuccess) { err = "hipMalloc(const) failed"; return; }
     r.shape = {n}; r.numel = (size_t)n;
     (void)launch_fill_f32(r.p, value, n, pack_stream);
-    u->w[name] = r;
+    u->w.recs[name] = r;
   }
 
   // ---- PromptEncoder (reference model3.py:382-433): ConvLayer `pre` (k=1) -> n x EncSALayer
@@ -2254,8 +2230,7 @@ extern "C" void dv_penc_destroy(dv_penc* p) {
   if (!p) return;
   (void)hipDeviceSynchronize();
   unet_release_prepared(&p->core);
-  for (auto& kv : p->core.w)
-    if (kv.second.p) (void)hipFree(kv.second.p);
+  p->core.w.free_all();
   delete p;
 }
 
@@ -2300,20 +2275,6 @@ extern "C" int dv_penc_prepare(dv_penc* p, int32_t B, int32_t L, int32_t precisi
   u->prepared = true;
   u->weights_dirty = false;
   u->generation = ++g_generation;
-  return DV_OK;
-}
-
-// (DVITS_SYNC_OPS=1, development: every operation is announced on stderr and waited for - a device fault names its launch)
-static int run_ops(const std::vector<OpFn>& ops, hipStream_t st, const char* what, const std::vector<dv_unet::OpMeta>* meta = nullptr) {
-  static const bool sync_ops = [] { const char* e = getenv("DVITS_SYNC_OPS"); return e && e[0] == '1'; }();
-  int i = 0;
-  for (const OpFn& f : ops) {
-    if (sync_ops) fprintf(stderr, "[dvits] %s op %d %s %s\n", what, i, meta && i < (int)meta->size() ? (*meta)[i].kind : "", meta && i < (int)meta->size() ? (*meta)[i].desc.c_str() : "");
-    hipError_t e = f(st);
-    if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "%s: op %d failed to launch: %s", what, i, hipGetErrorString(e));
-    if (sync_ops && (e = hipStreamSynchronize(st)) != hipSuccess) return dv_fail(DV_ERR_HIP, "%s: op %d failed: %s", what, i, hipGetErrorString(e));
-    ++i;
-  }
   return DV_OK;
 }
 
@@ -2558,7 +2519,9 @@ int dv_unet_enqueue(dv_unet* u, const float* x, int cx, const float* cond, const
     }
     return DV_OK;
   }
-  if (!u->persist_on) return run_ops(u->step_ops, st, "forward", &u->step_meta);
+  if (!u->persist_on) return run_ops(u->step_ops, st, "forward", [u](int i) {
+    return i < (int)u->step_meta.size() ? std::string(u->step_meta[(size_t)i].kind) + " " + u->step_meta[(size_t)i].desc : std::string();
+  });
   for (int i = 0; i < u->p_begin; ++i) {
     hipError_t e = u->step_ops[i](st);
     if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "forward: op %d failed to launch: %s", i, hipGetErrorString(e));
@@ -2703,31 +2666,8 @@ int dv_unet_dims(const dv_unet* u, int* B, int* T, int* cin, int* cout, int64_t*
 }
 
 static int probe_copy(dv_unet* u, const char* name, float* host_out, int64_t capacity, int64_t* dims) {
-  for (const Probe& p : u->probes) {
-    if (p.name == name) {
-      const int64_t n = (int64_t)u->B * p.T * p.C;
-      if (dims) { dims[0] = u->B; dims[1] = p.T; dims[2] = p.C; }
-      if (!host_out) return DV_OK;
-      if (capacity < n) return dv_fail(DV_ERR_INVALID, "probe buffer too small");
-      HIPCHK(hipDeviceSynchronize());
-      if (!p.p) {   // split planes: fp32 value = hi + lo (bf16 bits are the upper half of an fp32); B pieces of T frames, Tp frames apart
-        const size_t row = (size_t)p.T * p.C, pitch = (size_t)p.Tp * p.C;
-        std::vector<bf16_t> h((size_t)n), l;
-        HIPCHK(hipMemcpy2D(h.data(), row * sizeof(bf16_t), p.hi, pitch * sizeof(bf16_t), row * sizeof(bf16_t), (size_t)u->B, hipMemcpyDeviceToHost));
-        if (p.lo) {
-          l.resize((size_t)n);
-          HIPCHK(hipMemcpy2D(l.data(), row * sizeof(bf16_t), p.lo, pitch * sizeof(bf16_t), row * sizeof(bf16_t), (size_t)u->B, hipMemcpyDeviceToHost));
-        }
-        auto f32 = [](bf16_t b) { const uint32_t w = (uint32_t)b << 16; float f; memcpy(&f, &w, 4); return f; };
-        for (int64_t i = 0; i < n; ++i) host_out[i] = p.scale * (f32(h[(size_t)i]) + (p.lo ? f32(l[(size_t)i]) : 0.f));
-        return DV_OK;
-      }
-      // (rows of a padded row space - Builder::pitch - are skipped: B pieces of T frames, Tp frames apart)
-      HIPCHK(hipMemcpy2D(host_out, (size_t)p.T * p.C * sizeof(float), p.p, (size_t)p.Tp * p.C * sizeof(float),
-                         (size_t)p.T * p.C * sizeof(float), (size_t)u->B, hipMemcpyDeviceToHost));
-      return DV_OK;
-    }
-  }
+  for (const Probe& p : u->probes)
+    if (p.name == name) return probe_rows(p.p, p.hi, p.lo, p.scale, u->B, p.T, p.C, p.Tp, host_out, capacity, dims);
   return dv_fail(DV_ERR_INVALID, "no probe named %s (prepare with DVITS_KEEP_INTERMEDIATES=1%s)", name,
                  u->tap_mode ? "; the tapped production plan holds no such tensor" : "");
 }

@@ -11,114 +11,45 @@
 // Weight norm is folded when the weights are packed (k_wn_fold).  Padding rows hold exact zeros after every step.
 // DVITS_KEEP_INTERMEDIATES=1: every layer writes buffers of its own (and its gated activations) so that the probes stay valid;
 // the launch count is the same.
-#include "../../include/dvits_hip.h"
-#include "dv_common.h"
+#include "engine_core.h"
 
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <string>
-#include <vector>
-
-int dv_fail(int code, const char* fmt, ...);
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return dv_fail(DV_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
-namespace {
-
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 enum { QENC_MAX_T = 16384 };                     // the aligner's own limit on frames (dv_op_mas_path)
 
-struct QW { float* p = nullptr; std::vector<int64_t> shape; size_t numel = 0; };
-struct QPacked { bf16_t* hi = nullptr; bf16_t* lo = nullptr; float* bias = nullptr; int Kp = 0, N = 0, N_pad = 0; };
-struct QProbe { std::string name; const float* p; int C; };
-typedef std::function<hipError_t(hipStream_t)> QOp;
-
-}  // namespace
-
-struct dv_qenc {
+struct dv_qenc : RowEngine {
   dv_qenc_cfg cfg{};
-  std::map<std::string, QW> w;
-  bool weights_dirty = true;
-  bool prepared = false, keep = false;
-  int B = 0, T = 0, precision = 0;
-  std::vector<void*> owned, owned_w;         // per prepared shape / packed weights (kept while the weights stay the same)
   std::vector<void*> temp_w;                 // packing intermediates (folded fp32 weights, planes before the fragment relayout): freed
                                              // once the prepare that made them has drained
-  std::map<std::string, QPacked> packed;
-  const float* cond_w = nullptr;             // cond_layer with its weight norm folded [2H L, gin]
-  std::vector<std::unique_ptr<GemmParams>> gemm_store;
-  std::vector<QOp> ops;
-  std::vector<QProbe> probes;
-  bf16_t* zero_page = nullptr;
-  double flops = 0;
+  const float* cond_w = nullptr;             // cond_layer with its weight norm folded [2H L, gin] (in `owned_w`)
   struct { const float* y = nullptr; const int64_t* lengths = nullptr; const float* g = nullptr; const float* noise = nullptr;
            float* z = nullptr; float* m = nullptr; float* logs = nullptr; } io;
 };
 
 namespace {
 
-void qenc_release_temp(dv_qenc* q) {
-  for (void* p : q->temp_w) (void)hipFree(p);
-  q->temp_w.clear();
-}
-void qenc_release_packed(dv_qenc* q) {
-  qenc_release_temp(q);
-  for (void* p : q->owned_w) (void)hipFree(p);
-  q->owned_w.clear(); q->packed.clear(); q->cond_w = nullptr;
-}
 void qenc_release_prepared(dv_qenc* q, bool keep_packed) {
-  for (void* p : q->owned) (void)hipFree(p);
-  q->owned.clear(); q->gemm_store.clear(); q->ops.clear(); q->probes.clear();
-  q->zero_page = nullptr; q->prepared = false; q->flops = 0;
-  if (!keep_packed) qenc_release_packed(q);
+  q->release_prepared();
+  if (!keep_packed) { free_owned(q->temp_w); q->release_packed(); q->cond_w = nullptr; }
 }
 
-struct QPlan {
+struct QPlan : RowPlan {
   dv_qenc* q;
-  int B, T, M, H, C, Cin, Kp, L, gin;
-  std::string err;
-  hipStream_t st = nullptr;
+  int H, C, Cin, Kp, L, gin;
 
-  const QW* raw(const std::string& name, size_t numel) {
-    auto it = q->w.find(name);
-    if (it == q->w.end()) { if (err.empty()) err = "missing weight: " + name; return nullptr; }
-    if (it->second.numel != numel) { if (err.empty()) err = "weight shape mismatch: " + name; return nullptr; }
-    return &it->second;
-  }
-  const float* W(const std::string& name, size_t numel) { const QW* r = raw(name, numel); return r ? r->p : nullptr; }
-  template <typename X> X* dmalloc(size_t elems, std::vector<void*>& owner, bool zero) {
-    void* p = nullptr;
-    const size_t bytes = elems * sizeof(X);
-    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err.empty()) err = "hipMalloc failed"; return nullptr; }
-    owner.push_back(p);
-    if (zero) (void)hipMemsetAsync(p, 0, bytes ? bytes : 16, st);
-    return reinterpret_cast<X*>(p);
-  }
   // weight_g * weight_v / ||weight_v|| of a weight-normed convolution `name` with N output channels of per_row weights each
   const float* folded(const std::string& name, int N, int per_row, std::vector<void*>& owner) {
     const float* v = W(name + ".weight_v", (size_t)N * per_row);
     const float* g = W(name + ".weight_g", (size_t)N);
     float* w = dmalloc<float>((size_t)N * per_row, owner, false);
     if (!v || !g || !w) return nullptr;
-    if (launch_wn_fold(v, g, w, N, per_row, st) != hipSuccess) { err = "weight norm launch failed"; return nullptr; }
+    if (launch_wn_fold(v, g, w, N, per_row, st) != hipSuccess) { err.set(DV_ERR_HIP, "weight norm launch failed"); return nullptr; }
     return w;
   }
   // src fp32 [N, Cw, taps] -> split planes [rup(N, 128)][Kp] (K order: tap, channel), optionally in GEGLU row order and fragment-major
-  const QPacked* pack(const std::string& key, const float* src, const float* bias, int N, int Cw, int taps, int Kp_, bool gate, bool frag) {
+  const PackedW3* pack(const std::string& key, const float* src, const float* bias, int N, int Cw, int taps, int Kp_, bool gate, bool frag) {
     auto it = q->packed.find(key);
     if (it != q->packed.end()) return &it->second;
     if (!src || !bias) return nullptr;
-    QPacked pw;
+    PackedW3 pw;
     pw.N = N; pw.Kp = Kp_; pw.N_pad = rup(N, 128);
     const size_t elems = (size_t)pw.N_pad * Kp_;
     pw.hi = dmalloc<bf16_t>(elems, frag ? q->temp_w : q->owned_w, true);
@@ -128,47 +59,31 @@ struct QPlan {
     PackSpec s{};
     s.src = src; s.N = N; s.kind = taps > 1 ? 1 : 0; s.C = Cw; s.taps = taps; s.c_pad = taps > 1 ? Cw : Kp_; s.k_off = 0; s.n_off = 0;
     s.kscale = nullptr; s.geglu = gate ? 1 : 0;
-    if (launch_pack_weight(s, pw.hi, pw.lo, Kp_, st) != hipSuccess) { err = "pack_weight launch failed"; return nullptr; }
-    if (hipMemcpyAsync(pw.bias, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { err = "bias copy failed"; return nullptr; }
+    if (launch_pack_weight(s, pw.hi, pw.lo, Kp_, st) != hipSuccess) { err.set(DV_ERR_HIP, "pack_weight launch failed"); return nullptr; }
+    if (hipMemcpyAsync(pw.bias, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { err.set(DV_ERR_HIP, "bias copy failed"); return nullptr; }
     if (frag) {
       bf16_t* fh = dmalloc<bf16_t>(elems, q->owned_w, false);
       bf16_t* fl = dmalloc<bf16_t>(elems, q->owned_w, false);
       if (!fh || !fl) return nullptr;
       if (launch_relayout_frag(pw.hi, fh, pw.N_pad, Kp_, st) != hipSuccess || launch_relayout_frag(pw.lo, fl, pw.N_pad, Kp_, st) != hipSuccess) {
-        err = "relayout launch failed"; return nullptr;
+        err.set(DV_ERR_HIP, "relayout launch failed"); return nullptr;
       }
       pw.hi = fh; pw.lo = fl;
     }
     q->packed[key] = pw;
     return &q->packed[key];
   }
-  GemmParams gp(int N) {
-    GemmParams g{};
-    g.nseg = 1; g.B = B; g.T_out = g.T_in = g.Tv_out = g.Tv_in = g.T_virt = T; g.stride = 1; g.up_mode = UP_NONE;
-    g.M = M; g.N = N; g.epi = EPI_STORE; g.ldo = N; g.ldres = N; g.zero_page = q->zero_page;
-    return g;
-  }
-  void gemm(GemmParams g, const QPacked* pw, int k_real) {
-    g.w_hi = pw->hi; g.w_lo = pw->lo; g.Kp = pw->Kp; g.N_pad = pw->N_pad; g.bias = pw->bias;
-    q->gemm_store.emplace_back(new GemmParams(g));
-    const GemmParams* p = q->gemm_store.back().get();
-    const int prec = q->precision;
-    q->ops.push_back([p, prec](hipStream_t s) { return launch_gemm(*p, prec, s); });
-    q->flops += 2.0 * (double)g.M * (double)g.N * (double)k_real;
-  }
-  void probe(const std::string& name, const float* p, int Cc) { if (q->keep) q->probes.push_back(QProbe{name, p, Cc}); }
-  int fail() { return dv_fail(err.rfind("hipMalloc", 0) == 0 ? DV_ERR_HIP : (err.rfind("missing", 0) == 0 || err.rfind("weight shape", 0) == 0) ? DV_ERR_MISSING_WEIGHT : DV_ERR_HIP, "%s", err.c_str()); }
+  int fail() const { return err.fail(); }
 
   int build() {
     dv_qenc* qq = q;
     const int Bn = B, Tn = T, Hn = H, Cn = C, Cinn = Cin, Kpn = Kp, ginn = gin, Nc = 2 * H * L;
     const size_t MH = (size_t)M * H;
-    q->zero_page = dmalloc<bf16_t>(DV_ZERO_PAGE_BYTES / 2, q->owned, true);
-    if (!q->zero_page) return fail();
+    if (!zero_page()) return fail();
 
     // ---- weights (once per weight set) ----
-    const QPacked* w_pre = pack("pre", W("pre.weight", (size_t)H * Cin), W("pre.bias", (size_t)H), H, Cin, 1, Kp, false, false);
-    const QPacked* w_proj = pack("proj", W("proj.weight", (size_t)2 * C * H), W("proj.bias", (size_t)2 * C), 2 * C, H, 1, H, false, false);
+    const PackedW3* w_pre = pack("pre", W("pre.weight", (size_t)H * Cin), W("pre.bias", (size_t)H), H, Cin, 1, Kp, false, false);
+    const PackedW3* w_proj = pack("proj", W("proj.weight", (size_t)2 * C * H), W("proj.bias", (size_t)2 * C), 2 * C, H, 1, H, false, false);
     if (!w_pre || !w_proj) return fail();
     const float* cond_b = nullptr;
     if (gin > 0) {
@@ -176,7 +91,7 @@ struct QPlan {
       cond_b = W("enc.cond_layer.bias", (size_t)Nc);
       if (!q->cond_w || !cond_b) return fail();
     }
-    std::vector<const QPacked*> w_in(L), w_rs(L);
+    std::vector<const PackedW3*> w_in(L), w_rs(L);
     for (int i = 0; i < L; ++i) {
       const std::string pi = "enc.in_layers." + std::to_string(i), pr = "enc.res_skip_layers." + std::to_string(i);
       const int N2 = i < L - 1 ? 2 * H : H;
@@ -215,7 +130,7 @@ struct QPlan {
     }
     {
       GemmParams g = gp(H);
-      g.seg[0] = GemmSeg{}; g.seg[0].a0_hi = in_hi; g.seg[0].a0_lo = in_lo; g.seg[0].c0 = Kp; g.seg[0].taps = 1; g.seg[0].pad = 0;
+      g.seg[0] = seg1(in_hi, in_lo, Kp, 1, 0);
       g.out = xs[0].x; g.out_hi = xs[0].hi; g.out_lo = xs[0].lo; g.rowmask = keep;
       gemm(g, w_pre, Cin);
     }
@@ -244,20 +159,20 @@ struct QPlan {
       });
       q->flops += 2.0 * (double)M * ((double)5 * H * 2 * H + (double)H * (last ? H : 2 * H));
       const std::string li = "layer" + std::to_string(i);
-      if (q->keep) q->probes.push_back(QProbe{li + ".acts", acts[i], H});
+      if (q->keep) probe(li + ".acts", acts[i], H);
       if (!last) probe(li + ".x", xs[nxt].x, H);
       probe(li + ".skip", p.skip_out, H);
       cur = nxt;
     }
     {
       GemmParams g = gp(2 * C);
-      g.seg[0] = GemmSeg{}; g.seg[0].a0_hi = s_hi; g.seg[0].a0_lo = s_lo; g.seg[0].c0 = H; g.seg[0].taps = 1; g.seg[0].pad = 0;
+      g.seg[0] = seg1(s_hi, s_lo, H, 1, 0);
       g.out = z; g.rowmask = keep;
       gemm(g, w_proj, H);
     }
     probe("proj", z, 2 * C);
     q->ops.push_back([=](hipStream_t s) { return launch_wn_store(z, qq->io.noise, qq->io.lengths, qq->io.z, qq->io.m, qq->io.logs, Bn, Tn, Cn, s); });
-    if (!err.empty()) return fail();
+    if (err) return fail();
     return DV_OK;
   }
 };
@@ -283,30 +198,12 @@ extern "C" void dv_qenc_destroy(dv_qenc* q) {
   if (!q) return;
   (void)hipDeviceSynchronize();
   qenc_release_prepared(q, false);
-  for (auto& kv : q->w)
-    if (kv.second.p) (void)hipFree(kv.second.p);
+  q->w.free_all();
   delete q;
 }
 
 extern "C" int dv_qenc_set_weight(dv_qenc* q, const char* name, const void* dev_ptr, const int64_t* shape, int32_t ndim) {
-  if (!q || !name || !dev_ptr || !shape || ndim < 1 || ndim > 4) return dv_fail(DV_ERR_INVALID, "dv_qenc_set_weight: bad argument");
-  size_t n = 1;
-  std::vector<int64_t> sh(shape, shape + ndim);
-  for (auto s : sh) {
-    if (s <= 0) return dv_fail(DV_ERR_INVALID, "dv_qenc_set_weight(%s): non-positive dimension", name);
-    n *= (size_t)s;
-  }
-  QW& r = q->w[name];
-  if (r.numel != n) {
-    if (r.p) (void)hipFree(r.p);
-    r.p = nullptr; r.numel = 0;
-    HIPCHK(hipMalloc((void**)&r.p, n * sizeof(float)));
-  }
-  r.shape = sh; r.numel = n;
-  HIPCHK(hipMemcpy(r.p, dev_ptr, n * sizeof(float), hipMemcpyDeviceToDevice));
-  q->weights_dirty = true;
-  q->prepared = false;
-  return DV_OK;
+  return row_set_weight(q, name, dev_ptr, shape, ndim, "dv_qenc_set_weight");
 }
 
 extern "C" int dv_qenc_prepare(dv_qenc* q, int32_t B, int32_t T, int32_t precision) {
@@ -333,12 +230,12 @@ extern "C" int dv_qenc_prepare(dv_qenc* q, int32_t B, int32_t T, int32_t precisi
   const char* keep = getenv("DVITS_KEEP_INTERMEDIATES");
   q->keep = keep && keep[0] == '1';
   QPlan pl{};
-  pl.q = q; pl.B = B; pl.T = T; pl.M = B * T;
+  pl.q = q; pl.e = q; pl.B = B; pl.T = T; pl.M = B * T;
   pl.H = c.hidden_channels; pl.C = c.out_channels; pl.Cin = c.in_channels; pl.Kp = rup(c.in_channels, 64); pl.L = c.n_layers; pl.gin = c.gin_channels;
   int rc = pl.build();
   if (rc != DV_OK) { qenc_release_prepared(q, false); q->weights_dirty = true; return rc; }
   HIPCHK(hipDeviceSynchronize());
-  qenc_release_temp(q);
+  free_owned(q->temp_w);
   q->prepared = true;
   q->weights_dirty = false;
   return DV_OK;
@@ -350,21 +247,10 @@ extern "C" int dv_qenc_forward(dv_qenc* q, const float* y, const int64_t* length
   if (!q->prepared) return dv_fail(DV_ERR_STATE, "dv_qenc_forward before dv_qenc_prepare");
   if (g && q->cfg.gin_channels == 0) return dv_fail(DV_ERR_INVALID, "dv_qenc_forward: g given, but the encoder has no cond_layer (gin_channels = 0)");
   q->io.y = y; q->io.lengths = lengths; q->io.g = g; q->io.noise = noise; q->io.z = z; q->io.m = m; q->io.logs = logs;
-  int i = 0;
-  for (const QOp& f : q->ops) {
-    hipError_t e = f((hipStream_t)stream);
-    if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "posterior encoder: op %d failed to launch: %s", i, hipGetErrorString(e));
-    ++i;
-  }
-  return DV_OK;
+  return run_ops(q->ops, (hipStream_t)stream, "posterior encoder");
 }
 
-extern "C" int dv_qenc_stats(dv_qenc* q, int64_t* n_launch, double* flops) {
-  if (!q || !q->prepared) return dv_fail(DV_ERR_STATE, "dv_qenc_stats before prepare");
-  if (n_launch) *n_launch = (int64_t)q->ops.size();
-  if (flops) *flops = q->flops;
-  return DV_OK;
-}
+extern "C" int dv_qenc_stats(dv_qenc* q, int64_t* n_launch, double* flops) { return row_stats(q, n_launch, flops, "dv_qenc"); }
 
 extern "C" int dv_qenc_time_layers(dv_qenc* q, int32_t reps, void* stream, float* us_per_pass) {
   if (!q || !us_per_pass || reps < 1) return dv_fail(DV_ERR_INVALID, "dv_qenc_time_layers: bad argument");
@@ -375,11 +261,10 @@ extern "C" int dv_qenc_time_layers(dv_qenc* q, int32_t reps, void* stream, float
   HIPCHK(hipEventCreate(&e0));
   HIPCHK(hipEventCreate(&e1));
   HIPCHK(hipEventRecord(e0, st));
-  for (int r = 0; r < reps; ++r)
-    for (int i = 2; i < 2 + L; ++i) {
-      hipError_t e = q->ops[(size_t)i](st);
-      if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "posterior encoder: op %d failed to launch: %s", i, hipGetErrorString(e));
-    }
+  for (int r = 0; r < reps; ++r) {
+    int rc = run_ops(q->ops.data() + 2, (size_t)L, st, "posterior encoder layers");
+    if (rc != DV_OK) return rc;
+  }
   HIPCHK(hipEventRecord(e1, st));
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0.f;
@@ -390,17 +275,5 @@ extern "C" int dv_qenc_time_layers(dv_qenc* q, int32_t reps, void* stream, float
 }
 
 extern "C" int dv_qenc_probe(dv_qenc* q, const char* name, float* host_out, int64_t capacity, int64_t* dims) {
-  if (!q || !name) return dv_fail(DV_ERR_INVALID, "dv_qenc_probe: null argument");
-  if (!q->prepared) return dv_fail(DV_ERR_STATE, "dv_qenc_probe before dv_qenc_prepare");
-  for (const QProbe& p : q->probes) {
-    if (p.name != name) continue;
-    const int64_t n = (int64_t)q->B * q->T * p.C;
-    if (dims) { dims[0] = q->B; dims[1] = q->T; dims[2] = p.C; }
-    if (!host_out) return DV_OK;
-    if (capacity < n) return dv_fail(DV_ERR_INVALID, "probe buffer too small");
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(host_out, p.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    return DV_OK;
-  }
-  return dv_fail(DV_ERR_INVALID, "no probe named %s (prepare with DVITS_KEEP_INTERMEDIATES=1)", name);
+  return row_probe(q, name, host_out, capacity, dims, "dv_qenc");
 }

@@ -15,8 +15,7 @@
 // identity and is not replayed.
 // Classifier-free guidance (dv_plan_set_guidance) wraps every EVAL: [x | x] -> the network at 2B rows -> x0_u + g (x0_c - x0_u)
 // into the history slot (kernels_guide.hip) - the reference's guided noise is linear in the two data predictions.
-#include "../../include/dvits_hip.h"
-#include "dv_common.h"
+#include "engine_core.h"
 
 #include <array>
 #include <cmath>
@@ -26,19 +25,11 @@
 #include <string>
 #include <vector>
 
-int dv_fail(int code, const char* fmt, ...);
 struct dv_unet;
 int dv_unet_enqueue(dv_unet* u, const float* x, int cx, const float* cond, const float* t, float* y, hipStream_t st, int eval_idx);
 int dv_unet_temb_all(dv_unet* u, const float* t_all, int n_evals, hipStream_t st);
 int dv_unet_dims(const dv_unet* u, int* B, int* T, int* cin, int* cout, int64_t* gen);
 int dv_unet_health(const dv_unet* u);
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return dv_fail(DV_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
 
 namespace {
 

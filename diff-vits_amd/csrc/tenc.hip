@@ -12,32 +12,13 @@
 //   k_gemm proj (N = 2C, row mask) -> k_tenc_store_nct: x * mask, m, logs channels-first
 // Padding rows are kept at zero after every step (the reference lets them drift and masks them where they are read: keys, the
 // feed-forward's input, the outputs - no valid row ever depends on one).
-#include "../../include/dvits_hip.h"
-#include "dv_common.h"
+#include "engine_core.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <string>
-#include <vector>
-
-int dv_fail(int code, const char* fmt, ...);
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return dv_fail(DV_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
 
 namespace {
 
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
+// (not misc_body.h's split4: this one rounds with integer arithmetic, that one with the packed hardware convert - they may differ on NaN)
 __device__ __forceinline__ void tenc_split4(const float4 v, uint2& h, uint2& l) {
   auto rne = [](float f) { unsigned u = __float_as_uint(f); u += 0x7fffu + ((u >> 16) & 1u); return u >> 16; };
   const unsigned h0 = rne(v.x), h1 = rne(v.y), h2 = rne(v.z), h3 = rne(v.w);
@@ -138,145 +119,86 @@ __global__ void k_tenc_scale(const float* __restrict__ in, float* __restrict__ o
   if (i < n) out[i] = in[i] * s;
 }
 
-struct TW { float* p = nullptr; std::vector<int64_t> shape; size_t numel = 0; };
-struct TPacked { bf16_t* hi = nullptr; bf16_t* lo = nullptr; float* bias = nullptr; int Kp = 0, N = 0, N_pad = 0; };
-struct TProbe { std::string name; const float* p; const bf16_t* hi; const bf16_t* lo; int C; };
-typedef std::function<hipError_t(hipStream_t)> TOp;
-
 }  // namespace
 
-struct dv_tenc {
+struct dv_tenc : RowEngine {
   dv_tenc_cfg cfg{};
-  std::map<std::string, TW> w;
-  bool weights_dirty = true;
-  bool prepared = false, keep = false;
-  int B = 0, T = 0, precision = 0;
-  std::vector<void*> owned, owned_w;         // per prepared shape / packed weights (kept while the weights stay the same)
-  std::map<std::string, TPacked> packed;
-  std::map<std::string, void*> bufs;
-  std::vector<std::unique_ptr<GemmParams>> gemm_store;
-  std::vector<TOp> ops;
-  std::vector<TProbe> probes;
-  bf16_t* zero_page = nullptr;
-  float* qscale_vec = nullptr;
-  double flops = 0;
+  std::map<std::string, void*> bufs;         // (in `owned`)
+  float* qscale_vec = nullptr;               // (in `owned_w`)
   struct { const int64_t* ids = nullptr; const int64_t* tone = nullptr; const int64_t* lang = nullptr; const int64_t* lengths = nullptr;
            const float* g = nullptr; float* x = nullptr; float* m = nullptr; float* logs = nullptr; } io;
 };
 
 namespace {
 
-void tenc_release_packed(dv_tenc* t) {
-  for (void* p : t->owned_w) (void)hipFree(p);
-  t->owned_w.clear(); t->packed.clear(); t->qscale_vec = nullptr;
-}
 void tenc_release_prepared(dv_tenc* t, bool keep_packed) {
-  for (void* p : t->owned) (void)hipFree(p);
-  t->owned.clear(); t->bufs.clear(); t->gemm_store.clear(); t->ops.clear(); t->probes.clear();
-  t->zero_page = nullptr; t->prepared = false; t->flops = 0;
-  if (!keep_packed) tenc_release_packed(t);
+  t->release_prepared();
+  t->bufs.clear();
+  if (!keep_packed) { t->release_packed(); t->qscale_vec = nullptr; }
 }
 
 // The planner of one prepare: packs the weights (once per weight set), sizes the buffers, emits the launches.
-struct TPlan {
+struct TPlan : RowPlan {
   dv_tenc* t;
-  int B, T, M, H, F, C, nh, d, ks, win, L;
-  std::string err;
-  hipStream_t st = nullptr;
+  int H, F, C, nh, d, ks, win, L;
 
-  const TW* raw(const std::string& name, size_t numel) {
-    auto it = t->w.find(name);
-    if (it == t->w.end()) { if (err.empty()) err = "missing weight: " + name; return nullptr; }
-    if (it->second.numel != numel) { if (err.empty()) err = "weight shape mismatch: " + name; return nullptr; }
-    return &it->second;
-  }
-  const float* W(const std::string& name, size_t numel) { const TW* r = raw(name, numel); return r ? r->p : nullptr; }
-  template <typename X> X* dmalloc(size_t bytes, std::vector<void*>& owner, bool zero) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err.empty()) err = "hipMalloc failed"; return nullptr; }
-    owner.push_back(p);
-    if (zero) (void)hipMemsetAsync(p, 0, bytes ? bytes : 16, st);
-    return reinterpret_cast<X*>(p);
-  }
   // activation buffers: one set shared by all layers, or (DVITS_KEEP_INTERMEDIATES=1) one per layer so that probes stay valid
   template <typename X> X* buf(const std::string& name, int layer, size_t elems) {
     const std::string key = t->keep ? name + "." + std::to_string(layer) : name;
     auto it = t->bufs.find(key);
     if (it != t->bufs.end()) return reinterpret_cast<X*>(it->second);
-    X* p = dmalloc<X>(elems * sizeof(X), t->owned, false);
+    X* p = dmalloc<X>(elems, t->owned, false);
     t->bufs[key] = p;
     return p;
   }
   struct Piece { std::string w; int N, kind, Cw, taps, n_off; const float* kscale; };
   struct BiasPiece { const float* p; int N, n_off; };
-  const TPacked* pack(const std::string& key, int N, int Kp, const std::vector<Piece>& pieces, const std::vector<BiasPiece>& biases) {
+  const PackedW3* pack(const std::string& key, int N, int Kp, const std::vector<Piece>& pieces, const std::vector<BiasPiece>& biases) {
     auto it = t->packed.find(key);
     if (it != t->packed.end()) return &it->second;
-    TPacked pw;
+    PackedW3 pw;
     pw.N = N; pw.Kp = Kp; pw.N_pad = rup(N, 128);
     const size_t elems = (size_t)pw.N_pad * Kp;
-    pw.hi = dmalloc<bf16_t>(elems * 2, t->owned_w, true);
-    pw.lo = dmalloc<bf16_t>(elems * 2, t->owned_w, true);
-    pw.bias = dmalloc<float>((size_t)pw.N_pad * 4, t->owned_w, true);
+    pw.hi = dmalloc<bf16_t>(elems, t->owned_w, true);
+    pw.lo = dmalloc<bf16_t>(elems, t->owned_w, true);
+    pw.bias = dmalloc<float>((size_t)pw.N_pad, t->owned_w, true);
     if (!pw.hi || !pw.lo || !pw.bias) return nullptr;
     for (const Piece& pc : pieces) {
-      const TW* r = raw(pc.w, (size_t)pc.N * pc.Cw * pc.taps);
+      const RawW* r = raw(pc.w, (size_t)pc.N * pc.Cw * pc.taps);
       if (!r) return nullptr;
       PackSpec s{};
       s.src = r->p; s.N = pc.N; s.kind = pc.kind; s.C = pc.Cw; s.taps = pc.taps; s.c_pad = pc.Cw; s.k_off = 0; s.n_off = pc.n_off;
       s.kscale = pc.kscale; s.geglu = 0;
-      if (launch_pack_weight(s, pw.hi, pw.lo, Kp, st) != hipSuccess) { err = "pack_weight launch failed"; return nullptr; }
+      if (launch_pack_weight(s, pw.hi, pw.lo, Kp, st) != hipSuccess) { err.set(DV_ERR_HIP, "pack_weight launch failed"); return nullptr; }
     }
     for (const BiasPiece& bp : biases) {
       if (!bp.p) return nullptr;
-      if (hipMemcpyAsync(pw.bias + bp.n_off, bp.p, (size_t)bp.N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { err = "bias copy failed"; return nullptr; }
+      if (hipMemcpyAsync(pw.bias + bp.n_off, bp.p, (size_t)bp.N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { err.set(DV_ERR_HIP, "bias copy failed"); return nullptr; }
     }
     t->packed[key] = pw;
     return &t->packed[key];
   }
 
-  GemmParams gp(int N) {
-    GemmParams g{};
-    g.nseg = 1; g.B = B; g.T_out = g.T_in = g.Tv_out = g.Tv_in = g.T_virt = T; g.stride = 1; g.up_mode = UP_NONE;
-    g.M = M; g.N = N; g.epi = EPI_STORE; g.ldo = N; g.ldres = N; g.zero_page = t->zero_page;
-    return g;
-  }
-  static GemmSeg seg(const bf16_t* hi, const bf16_t* lo, int c, int taps, int pad) {
-    GemmSeg s{};
-    s.a0_hi = hi; s.a0_lo = lo; s.c0 = c; s.taps = taps; s.pad = pad;
-    return s;
-  }
-  void gemm(GemmParams g, const TPacked* pw, int k_real) {
-    g.w_hi = pw->hi; g.w_lo = pw->lo; g.Kp = pw->Kp; g.N_pad = pw->N_pad; g.bias = pw->bias;
-    t->gemm_store.emplace_back(new GemmParams(g));
-    const GemmParams* p = t->gemm_store.back().get();
-    const int prec = t->precision;
-    t->ops.push_back([p, prec](hipStream_t s) { return launch_gemm(*p, prec, s); });
-    t->flops += 2.0 * (double)g.M * (double)g.N * (double)k_real;
-  }
-  void probe(const std::string& name, const float* p, int Cc) { if (t->keep) t->probes.push_back(TProbe{name, p, nullptr, nullptr, Cc}); }
-
   int build() {
     dv_tenc* tt = t;
     const dv_tenc_cfg& c = t->cfg;
     const int Bn = B, Tn = T, Hn = H;
-    t->zero_page = dmalloc<bf16_t>(DV_ZERO_PAGE_BYTES, t->owned, true);
-    if (!t->zero_page) return dv_fail(DV_ERR_HIP, "%s", err.c_str());
+    if (!zero_page()) return err.fail();
     if (!t->qscale_vec) {
-      t->qscale_vec = dmalloc<float>((size_t)H * 4, t->owned_w, false);
-      if (!t->qscale_vec) return dv_fail(DV_ERR_HIP, "%s", err.c_str());
+      t->qscale_vec = dmalloc<float>((size_t)H, t->owned_w, false);
+      if (!t->qscale_vec) return err.fail();
       (void)launch_fill_f32(t->qscale_vec, 1.0f / sqrtf((float)d), H, st);
     }
     const float* e_id = W("emb.weight", (size_t)c.n_vocab * H);
     const float* e_tone = W("tone_emb.weight", (size_t)c.n_tones * H);
     const float* e_lang = W("language_emb.weight", (size_t)c.n_languages * H);
-    if (!e_id || !e_tone || !e_lang) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
+    if (!e_id || !e_tone || !e_lang) return err.fail();
 
     float* keep = buf<float>("keep", 0, (size_t)M);
     float* x = buf<float>("x", -1, (size_t)M * H);
     bf16_t* x_hi = buf<bf16_t>("x_hi", -1, (size_t)M * H);
     bf16_t* x_lo = buf<bf16_t>("x_lo", -1, (size_t)M * H);
-    if (!keep || !x || !x_hi || !x_lo) return dv_fail(DV_ERR_HIP, "%s", err.c_str());
+    if (!keep || !x || !x_hi || !x_lo) return err.fail();
     {
       const int nv = c.n_vocab, ntn = c.n_tones, nl = c.n_languages;
       const float sc = sqrtf((float)H);
@@ -294,36 +216,34 @@ struct TPlan {
       w_spk = W("encoder.spk_emb_linear.weight", (size_t)H * c.gin_channels);
       b_spk = W("encoder.spk_emb_linear.bias", (size_t)H);
       gl = buf<float>("gl", 0, (size_t)B * H);
-      if (!w_spk || !b_spk || !gl) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
+      if (!w_spk || !b_spk || !gl) return err.fail();
     }
 
     for (int i = 0; i < L; ++i) {
       const std::string li = std::to_string(i);
       const std::string pa = "encoder.attn_layers." + li + ".", pf = "encoder.ffn_layers." + li + ".";
       const std::string n1 = "encoder.norm_layers_1." + li + ".", n2 = "encoder.norm_layers_2." + li + ".";
-      const size_t HH = (size_t)H * H;
       // d^-1/2 rides on the packed q rows (a constant per-source-channel factor) and on the q bias
       float* bq = nullptr;
       if (!t->packed.count(pa + "qkv")) {
         const float* bq_raw = W(pa + "conv_q.bias", (size_t)H);
-        bq = dmalloc<float>((size_t)H * 4, t->owned_w, false);
-        if (!bq_raw || !bq) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
+        bq = dmalloc<float>((size_t)H, t->owned_w, false);
+        if (!bq_raw || !bq) return err.fail();
         hipLaunchKernelGGL(k_tenc_scale, dim3((H + 255) / 256), dim3(256), 0, st, bq_raw, bq, 1.0f / sqrtf((float)d), H);
       }
-      const TPacked* w_qkv = pack(pa + "qkv", 3 * H, H,
+      const PackedW3* w_qkv = pack(pa + "qkv", 3 * H, H,
                                   {{pa + "conv_q.weight", H, 0, H, 1, 0, t->qscale_vec}, {pa + "conv_k.weight", H, 0, H, 1, H, nullptr},
                                    {pa + "conv_v.weight", H, 0, H, 1, 2 * H, nullptr}},
                                   {{bq, H, 0}, {W(pa + "conv_k.bias", (size_t)H), H, H}, {W(pa + "conv_v.bias", (size_t)H), H, 2 * H}});
-      const TPacked* w_o = pack(pa + "o", H, H, {{pa + "conv_o.weight", H, 0, H, 1, 0, nullptr}}, {{W(pa + "conv_o.bias", (size_t)H), H, 0}});
-      const TPacked* w_f1 = pack(pf + "c1", F, ks * H, {{pf + "conv_1.weight", F, 1, H, ks, 0, nullptr}}, {{W(pf + "conv_1.bias", (size_t)F), F, 0}});
-      const TPacked* w_f2 = pack(pf + "c2", H, ks * F, {{pf + "conv_2.weight", H, 1, F, ks, 0, nullptr}}, {{W(pf + "conv_2.bias", (size_t)H), H, 0}});
+      const PackedW3* w_o = pack(pa + "o", H, H, {{pa + "conv_o.weight", H, 0, H, 1, 0, nullptr}}, {{W(pa + "conv_o.bias", (size_t)H), H, 0}});
+      const PackedW3* w_f1 = pack(pf + "c1", F, ks * H, {{pf + "conv_1.weight", F, 1, H, ks, 0, nullptr}}, {{W(pf + "conv_1.bias", (size_t)F), F, 0}});
+      const PackedW3* w_f2 = pack(pf + "c2", H, ks * F, {{pf + "conv_2.weight", H, 1, F, ks, 0, nullptr}}, {{W(pf + "conv_2.bias", (size_t)H), H, 0}});
       const float* ek = W(pa + "emb_rel_k", (size_t)(2 * win + 1) * d);
       const float* ev = W(pa + "emb_rel_v", (size_t)(2 * win + 1) * d);
       const float* g1 = W(n1 + "gamma", (size_t)H); const float* b1 = W(n1 + "beta", (size_t)H);
       const float* g2 = W(n2 + "gamma", (size_t)H); const float* b2 = W(n2 + "beta", (size_t)H);
-      (void)HH;
       if (!w_qkv || !w_o || !w_f1 || !w_f2 || !ek || !ev || !g1 || !b1 || !g2 || !b2)
-        return dv_fail(err.rfind("hipMalloc", 0) == 0 ? DV_ERR_HIP : DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
+        return err.fail();
 
       // the layer's input: x (fp32: conv_o's residual) and its split planes (the q|k|v operand)
       if (i == c.cond_layer_idx && c.gin_channels > 0) {
@@ -339,7 +259,7 @@ struct TPlan {
         float* xc = t->keep ? buf<float>("xc", i, (size_t)M * H) : x;
         bf16_t* xh = t->keep ? buf<bf16_t>("xc_hi", i, (size_t)M * H) : x_hi;
         bf16_t* xl = t->keep ? buf<bf16_t>("xc_lo", i, (size_t)M * H) : x_lo;
-        if (!xc || !xh || !xl) return dv_fail(DV_ERR_HIP, "%s", err.c_str());
+        if (!xc || !xh || !xl) return err.fail();
         t->ops.push_back([=](hipStream_t s) {
           if (!tt->io.g && xin == xc) return hipSuccess;
           hipLaunchKernelGGL(k_tenc_add_rows, dim3((Bn * Tn + 3) / 4), dim3(256), 0, s, xin, xc, xh, xl, tt->io.g ? gl : (const float*)nullptr,
@@ -358,9 +278,9 @@ struct TPlan {
       float* xn = buf<float>("x", i, (size_t)M * H);
       bf16_t* xn_hi = buf<bf16_t>("x_hi", i, (size_t)M * H); bf16_t* xn_lo = buf<bf16_t>("x_lo", i, (size_t)M * H);
       if (!qkv || !ao_hi || !ao_lo || !x1 || !y1 || !y1_hi || !y1_lo || !hh_hi || !hh_lo || !x2 || !xn || !xn_hi || !xn_lo)
-        return dv_fail(DV_ERR_HIP, "%s", err.c_str());
+        return err.fail();
 
-      { GemmParams g = gp(3 * H); g.seg[0] = seg(x_hi, x_lo, H, 1, 0); g.out = qkv; gemm(g, w_qkv, H); }
+      { GemmParams g = gp(3 * H); g.seg[0] = seg1(x_hi, x_lo, H, 1, 0); g.out = qkv; gemm(g, w_qkv, H); }
       {
         RelAttnParams a{};
         a.q = qkv; a.k = qkv + H; a.v = qkv + 2 * H; a.ldq = a.ldk = a.ldv = 3 * H;
@@ -369,22 +289,22 @@ struct TPlan {
         t->ops.push_back([a, tt](hipStream_t s) { RelAttnParams a2 = a; a2.lengths = tt->io.lengths; return launch_rel_attention(a2, s); });
         t->flops += 4.0 * B * nh * (double)T * T * d;
       }
-      { GemmParams g = gp(H); g.seg[0] = seg(ao_hi, ao_lo, H, 1, 0); g.epi = EPI_RESIDUAL; g.res = x; g.out = x1; g.rowmask = keep; gemm(g, w_o, H); }
+      { GemmParams g = gp(H); g.seg[0] = seg1(ao_hi, ao_lo, H, 1, 0); g.epi = EPI_RESIDUAL; g.res = x; g.out = x1; g.rowmask = keep; gemm(g, w_o, H); }
       probe("layer" + li + ".attn", x1, H);
       t->ops.push_back([=](hipStream_t s) { return launch_ln_affine(x1, g1, b1, keep, y1, y1_hi, y1_lo, Bn * Tn, Hn, 1e-5f, s); });
       probe("layer" + li + ".ln1", y1, H);
-      { GemmParams g = gp(F); g.seg[0] = seg(y1_hi, y1_lo, H, ks, (ks - 1) / 2); g.relu = 1; g.rowmask = keep; g.out_hi = hh_hi; g.out_lo = hh_lo; gemm(g, w_f1, ks * H); }
-      if (t->keep) t->probes.push_back(TProbe{"layer" + li + ".ffn1", nullptr, hh_hi, hh_lo, F});
-      { GemmParams g = gp(H); g.seg[0] = seg(hh_hi, hh_lo, F, ks, (ks - 1) / 2); g.epi = EPI_RESIDUAL; g.res = y1; g.out = x2; g.rowmask = keep; gemm(g, w_f2, ks * F); }
+      { GemmParams g = gp(F); g.seg[0] = seg1(y1_hi, y1_lo, H, ks, (ks - 1) / 2); g.relu = 1; g.rowmask = keep; g.out_hi = hh_hi; g.out_lo = hh_lo; gemm(g, w_f1, ks * H); }
+      if (t->keep) t->probes.push_back(RowProbe{"layer" + li + ".ffn1", nullptr, hh_hi, hh_lo, F});
+      { GemmParams g = gp(H); g.seg[0] = seg1(hh_hi, hh_lo, F, ks, (ks - 1) / 2); g.epi = EPI_RESIDUAL; g.res = y1; g.out = x2; g.rowmask = keep; gemm(g, w_f2, ks * F); }
       t->ops.push_back([=](hipStream_t s) { return launch_ln_affine(x2, g2, b2, keep, xn, xn_hi, xn_lo, Bn * Tn, Hn, 1e-5f, s); });
       probe("layer" + li, xn, H);
       x = xn; x_hi = xn_hi; x_lo = xn_lo;
     }
 
-    const TPacked* w_p = pack("proj", 2 * C, H, {{"proj.weight", 2 * C, 0, H, 1, 0, nullptr}}, {{W("proj.bias", (size_t)2 * C), 2 * C, 0}});
+    const PackedW3* w_p = pack("proj", 2 * C, H, {{"proj.weight", 2 * C, 0, H, 1, 0, nullptr}}, {{W("proj.bias", (size_t)2 * C), 2 * C, 0}});
     float* z = buf<float>("z", 0, (size_t)M * 2 * C);
-    if (!w_p || !z) return dv_fail(err.rfind("hipMalloc", 0) == 0 ? DV_ERR_HIP : DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
-    { GemmParams g = gp(2 * C); g.seg[0] = seg(x_hi, x_lo, H, 1, 0); g.out = z; g.rowmask = keep; gemm(g, w_p, H); }
+    if (!w_p || !z) return err.fail();
+    { GemmParams g = gp(2 * C); g.seg[0] = seg1(x_hi, x_lo, H, 1, 0); g.out = z; g.rowmask = keep; gemm(g, w_p, H); }
     probe("proj", z, 2 * C);
     {
       const float* xf = x;
@@ -395,7 +315,7 @@ struct TPlan {
         return hipGetLastError();
       });
     }
-    if (!err.empty()) return dv_fail(DV_ERR_MISSING_WEIGHT, "%s", err.c_str());
+    if (err) return err.fail();
     return DV_OK;
   }
 };
@@ -430,30 +350,12 @@ extern "C" void dv_tenc_destroy(dv_tenc* t) {
   if (!t) return;
   (void)hipDeviceSynchronize();
   tenc_release_prepared(t, false);
-  for (auto& kv : t->w)
-    if (kv.second.p) (void)hipFree(kv.second.p);
+  t->w.free_all();
   delete t;
 }
 
 extern "C" int dv_tenc_set_weight(dv_tenc* t, const char* name, const void* dev_ptr, const int64_t* shape, int32_t ndim) {
-  if (!t || !name || !dev_ptr || !shape || ndim < 1 || ndim > 4) return dv_fail(DV_ERR_INVALID, "dv_tenc_set_weight: bad argument");
-  size_t n = 1;
-  std::vector<int64_t> sh(shape, shape + ndim);
-  for (auto s : sh) {
-    if (s <= 0) return dv_fail(DV_ERR_INVALID, "dv_tenc_set_weight(%s): non-positive dimension", name);
-    n *= (size_t)s;
-  }
-  TW& r = t->w[name];
-  if (r.numel != n) {
-    if (r.p) (void)hipFree(r.p);
-    r.p = nullptr; r.numel = 0;
-    HIPCHK(hipMalloc((void**)&r.p, n * sizeof(float)));
-  }
-  r.shape = sh; r.numel = n;
-  HIPCHK(hipMemcpy(r.p, dev_ptr, n * sizeof(float), hipMemcpyDeviceToDevice));
-  t->weights_dirty = true;
-  t->prepared = false;
-  return DV_OK;
+  return row_set_weight(t, name, dev_ptr, shape, ndim, "dv_tenc_set_weight");
 }
 
 extern "C" int dv_tenc_prepare(dv_tenc* t, int32_t B, int32_t T, int32_t precision) {
@@ -474,7 +376,7 @@ extern "C" int dv_tenc_prepare(dv_tenc* t, int32_t B, int32_t T, int32_t precisi
   const char* keep = getenv("DVITS_KEEP_INTERMEDIATES");
   t->keep = keep && keep[0] == '1';
   TPlan pl{};
-  pl.t = t; pl.B = B; pl.T = T; pl.M = B * T;
+  pl.t = t; pl.e = t; pl.B = B; pl.T = T; pl.M = B * T;
   pl.H = t->cfg.hidden_channels; pl.F = t->cfg.filter_channels; pl.C = t->cfg.out_channels; pl.nh = t->cfg.n_heads;
   pl.d = pl.H / pl.nh; pl.ks = t->cfg.kernel_size; pl.win = t->cfg.window_size; pl.L = t->cfg.n_layers;
   int rc = pl.build();
@@ -491,41 +393,13 @@ extern "C" int dv_tenc_forward(dv_tenc* t, const int64_t* ids, const int64_t* to
   if (!t->prepared) return dv_fail(DV_ERR_STATE, "dv_tenc_forward before dv_tenc_prepare");
   t->io.ids = ids; t->io.tone = tone; t->io.lang = language; t->io.lengths = lengths; t->io.g = g;
   t->io.x = x; t->io.m = m; t->io.logs = logs;
-  int i = 0;
-  for (const TOp& f : t->ops) {
-    hipError_t e = f((hipStream_t)stream);
-    if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "text encoder: op %d failed to launch: %s", i, hipGetErrorString(e));
-    ++i;
-  }
-  return DV_OK;
+  return run_ops(t->ops, (hipStream_t)stream, "text encoder");
 }
 
-extern "C" int dv_tenc_stats(dv_tenc* t, int64_t* n_launch, double* flops) {
-  if (!t || !t->prepared) return dv_fail(DV_ERR_STATE, "dv_tenc_stats before prepare");
-  if (n_launch) *n_launch = (int64_t)t->ops.size();
-  if (flops) *flops = t->flops;
-  return DV_OK;
-}
+extern "C" int dv_tenc_stats(dv_tenc* t, int64_t* n_launch, double* flops) { return row_stats(t, n_launch, flops, "dv_tenc"); }
 
 extern "C" int dv_tenc_probe(dv_tenc* t, const char* name, float* host_out, int64_t capacity, int64_t* dims) {
-  if (!t || !name) return dv_fail(DV_ERR_INVALID, "dv_tenc_probe: null argument");
-  if (!t->prepared) return dv_fail(DV_ERR_STATE, "dv_tenc_probe before dv_tenc_prepare");
-  for (const TProbe& p : t->probes) {
-    if (p.name != name) continue;
-    const int64_t n = (int64_t)t->B * t->T * p.C;
-    if (dims) { dims[0] = t->B; dims[1] = t->T; dims[2] = p.C; }
-    if (!host_out) return DV_OK;
-    if (capacity < n) return dv_fail(DV_ERR_INVALID, "probe buffer too small");
-    HIPCHK(hipDeviceSynchronize());
-    if (p.p) { HIPCHK(hipMemcpy(host_out, p.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost)); return DV_OK; }
-    std::vector<bf16_t> h((size_t)n), l((size_t)n);   // split planes: value = hi + lo (bf16 bits are the upper half of an fp32)
-    HIPCHK(hipMemcpy(h.data(), p.hi, (size_t)n * sizeof(bf16_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(l.data(), p.lo, (size_t)n * sizeof(bf16_t), hipMemcpyDeviceToHost));
-    auto f32 = [](bf16_t b) { const uint32_t w = (uint32_t)b << 16; float f; memcpy(&f, &w, 4); return f; };
-    for (int64_t i = 0; i < n; ++i) host_out[i] = f32(h[(size_t)i]) + f32(l[(size_t)i]);
-    return DV_OK;
-  }
-  return dv_fail(DV_ERR_INVALID, "no probe named %s (prepare with DVITS_KEEP_INTERMEDIATES=1)", name);
+  return row_probe(t, name, host_out, capacity, dims, "dv_tenc");
 }
 
 extern "C" int dv_op_rel_attention(const float* q, const float* k, const float* v, const float* emb_k, const float* emb_v,

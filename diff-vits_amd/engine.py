@@ -103,6 +103,98 @@ class Voice:
             pass
 
 
+def module_signature(module):
+    """Cheap change detector (no state_dict() with its prefixed names per call): storage address + version counter of every
+    parameter / buffer; load_state_dict, .to() and in-place updates all move one of them."""
+    return (tuple((v.data_ptr(), v._version) for v in module.parameters())
+            + tuple((v.data_ptr(), v._version) for v in module.buffers()))
+
+
+def upload_state_dict(set_weight_fn, handle, module, what, transform=None, skip=None, hint=""):
+    """Every state-dict entry of `module` (but those `skip(name)` names), as contiguous float32 (after `transform(name, t32)`),
+    through the `what` entry point of the C ABI; one device synchronisation at the end."""
+    for name, t in module.state_dict().items():
+        if skip is not None and skip(name):
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("backend='hip' needs the module on a GPU (parameter %s is on %s)%s" % (name, t.device, hint))
+        t32 = t.detach().to(torch.float32)
+        if transform is not None:
+            t32 = transform(name, t32)
+        t32 = t32.contiguous()
+        shape = (C.c_int64 * t32.dim())(*t32.shape)
+        _lib.check(set_weight_fn(handle, name.encode(), _lib.ptr(t32), shape, t32.dim()), "%s(%s)" % (what, name))
+    torch.cuda.synchronize()
+
+
+def _native_stats(abi, handle):
+    """(launches per forward, flops) of the prepared schedule: `abi`_stats."""
+    n, f = C.c_int64(), C.c_double()
+    _lib.check(getattr(_lib.lib(), abi + "_stats")(handle, C.byref(n), C.byref(f)), abi + "_stats")
+    return n.value, f.value
+
+
+def _native_probe(abi, handle, name):
+    """`abi`_probe in its two calls: the dims, then the host copy."""
+    fn = getattr(_lib.lib(), abi + "_probe")
+    dims = (C.c_int64 * 3)()
+    _lib.check(fn(handle, name.encode(), None, 0, dims), abi + "_probe")
+    out = torch.empty(tuple(dims), dtype=torch.float32)
+    _lib.check(fn(handle, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims), abi + "_probe")
+    return out
+
+
+def speaker_rows(g, B, gin_channels, what):
+    """g [B, gin] / [B, gin, 1] or None -> contiguous float32 [B, gin] or None, for an encoder `what` with gin_channels."""
+    if g is None:
+        return None
+    if gin_channels == 0:
+        raise ValueError("this %s was built without speaker conditioning (gin_channels = 0)" % what)
+    gp = g.detach().to(torch.float32).reshape(B, -1).contiguous()
+    if gp.shape[1] != gin_channels:
+        raise ValueError("g must hold %d channels per utterance, got %s" % (gin_channels, tuple(g.shape)))
+    return gp
+
+
+class _NativeModule:
+    """One native handle of the C ABI family `_abi` (dv_penc / dv_tenc / dv_qenc) for one mirror module: creation, the
+    weight sync (re-uploaded when a parameter's data_ptr / _version moves), stats, probes and the guarded destroy."""
+    _abi = None
+    _transform = None      # staticmethod (name, float32 tensor) -> the tensor the ABI expects, or None
+    _skip = None           # staticmethod name -> True for state-dict entries the native side does not take, or None
+
+    def _create(self, module, cfg):
+        self.module = module
+        self._h = C.c_void_p()
+        _lib.check(getattr(_lib.lib(), self._abi + "_create")(C.byref(cfg), C.byref(self._h)), self._abi + "_create")
+        self._weight_sig = None
+        self._prepared = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                getattr(_lib.lib(), self._abi + "_destroy")(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def sync_weights(self):
+        sig = module_signature(self.module)
+        if sig == self._weight_sig:
+            return
+        upload_state_dict(getattr(_lib.lib(), self._abi + "_set_weight"), self._h, self.module, self._abi + "_set_weight",
+                          self._transform, self._skip)
+        self._weight_sig = sig
+        self._prepared = None
+
+    def stats(self):
+        return _native_stats(self._abi, self._h)
+
+    def probe(self, name):
+        """Named intermediate [B, T, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1 at prepare time)."""
+        return _native_probe(self._abi, self._h, name)
+
+
 class UNetEngine:
     def __init__(self, module):
         self.module = module
@@ -246,8 +338,6 @@ class UNetEngine:
         precision = precision or self.precision or default_precision()
         if precision not in _PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(_PRECISIONS))
-        # cheap change detector first (no state_dict() with its 701 prefixed names per call): storage address + version
-        # counter of every parameter / buffer; load_state_dict, .to() and in-place updates all move one of them
         sig = self._module_sig()
         if sig != self._sig:             # new parameters: every cached schedule is stale
             self._sig = sig
@@ -258,23 +348,14 @@ class UNetEngine:
         self._upload(self._cur)
 
     def _module_sig(self):
-        m = self.module
-        return tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
+        return module_signature(self.module)
 
     def _upload(self, slot):
         """Give `slot`'s native handle the module's current parameters if it does not have them yet."""
         if slot.weight_sig == self._sig:
             return
-        L = _lib.lib()
-        for name, t in self.module.state_dict().items():
-            if not t.is_cuda:
-                raise RuntimeError("backend='hip' needs the module on a GPU (parameter %s is on %s); "
-                                   "call .to('cuda') or construct with backend='torch'" % (name, t.device))
-            t32 = t.detach().to(torch.float32).contiguous()
-            shape = (C.c_int64 * t32.dim())(*t32.shape)
-            _lib.check(L.dv_unet_set_weight(slot.h, name.encode(), _lib.ptr(t32), shape, t32.dim()),
-                       "dv_unet_set_weight(%s)" % name)
-        torch.cuda.synchronize()
+        upload_state_dict(_lib.lib().dv_unet_set_weight, slot.h, self.module, "dv_unet_set_weight",
+                          hint="; call .to('cuda') or construct with backend='torch'")
         slot.weight_sig = self._sig
         slot.prepared = None
 
@@ -608,9 +689,7 @@ class UNetEngine:
         self.set_exclusive(True)
 
     def stats(self):
-        n, f = C.c_int64(), C.c_double()
-        _lib.check(_lib.lib().dv_unet_stats(self._h, C.byref(n), C.byref(f)), "dv_unet_stats")
-        return n.value, f.value
+        return _native_stats("dv_unet", self._h)
 
     def profile_forward(self, x, cond, t):
         """One eager forward with HIP events around every operation -> list of (kind, flops, ms, desc)."""
@@ -694,69 +773,42 @@ class UNetEngine:
         of its own that keeps all 132 names (two-GEMM feed-forward, no buffer reuse); `tap` keeps the production plan and copies
         each tensor out behind its producer (rows of kind "probe" in profile_forward name the taps) - `...transformer_blocks.0.ff`
         and the `conv1` that exist only normalised are not registered there and raise like any unknown name."""
-        dims = (C.c_int64 * 3)()
-        _lib.check(_lib.lib().dv_unet_probe(self._h, name.encode(), None, 0, dims), "dv_unet_probe")
-        out = torch.empty(tuple(dims), dtype=torch.float32)
-        _lib.check(_lib.lib().dv_unet_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims),
-                   "dv_unet_probe")
-        return out
+        return _native_probe("dv_unet", self._h, name)
 
     @property
     def handle(self):
         return self._h
 
 
-class PromptEncoderEngine:
+class PromptEncoderEngine(_NativeModule):
     """Native PromptEncoder (dv_penc_*, include/dvits_hip.h) for one mirror module (diff_vits_amd.model3.PromptEncoder)."""
+    _abi = "dv_penc"
 
     def __init__(self, module):
-        self.module = module
         c = _lib.PencCfg()
         c.in_channels, c.hidden_channels, c.out_channels = module.in_channels, module.hidden_size, module.out_channels
         c.n_layers, c.num_heads, c.ffn_kernel = module.num_layers, 8, 9
         self.out_channels = c.out_channels
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().dv_penc_create(C.byref(c), C.byref(self._h)), "dv_penc_create")
-        self._weight_sig = None
-        self._prepared = None
+        self._create(module, c)
         self.precision = None
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                _lib.lib().dv_penc_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+    @staticmethod
+    def _skip(name):
+        return name.startswith("g_proj.")          # speaker projection: applied by the mirror before the call
+
+    @staticmethod
+    def _transform(name, t32):
+        if name.endswith("conv.weight") and t32.dim() == 3:
+            if t32.shape[0] != 1:
+                raise ValueError("ConvTBC kernel_size %d is not used by PromptEncoder" % t32.shape[0])
+            t32 = t32[0].t()               # [1, C_in, C_out] -> [C_out, C_in] (include/dvits_hip.h)
+        return t32
 
     def sync_weights(self, precision=None):
         precision = precision or self.precision or default_precision()
         if precision not in _PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(_PRECISIONS))
-        # cheap change detector first (no state_dict() with its 701 prefixed names per call): storage address + version
-        # counter of every parameter / buffer; load_state_dict, .to() and in-place updates all move one of them
-        m = self.module
-        sig = tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
-        if sig != self._weight_sig:
-            sd = m.state_dict()
-            L = _lib.lib()
-            for name, t in sd.items():
-                if name.startswith("g_proj."):
-                    continue                       # speaker projection: applied by the mirror before the call
-                if not t.is_cuda:
-                    raise RuntimeError("backend='hip' needs the module on a GPU (parameter %s is on %s)" % (name, t.device))
-                t32 = t.detach().to(torch.float32)
-                if name.endswith("conv.weight") and t32.dim() == 3:
-                    if t32.shape[0] != 1:
-                        raise ValueError("ConvTBC kernel_size %d is not used by PromptEncoder" % t32.shape[0])
-                    t32 = t32[0].t()               # [1, C_in, C_out] -> [C_out, C_in] (include/dvits_hip.h)
-                t32 = t32.contiguous()
-                shape = (C.c_int64 * t32.dim())(*t32.shape)
-                _lib.check(L.dv_penc_set_weight(self._h, name.encode(), _lib.ptr(t32), shape, t32.dim()),
-                           "dv_penc_set_weight(%s)" % name)
-            torch.cuda.synchronize()
-            self._weight_sig = sig
-            self._prepared = None
+        super().sync_weights()
         if precision != self.precision:
             self.precision = precision
             self._prepared = None
@@ -778,28 +830,14 @@ class PromptEncoderEngine:
                    "dv_penc_forward")
         return out
 
-    def stats(self):
-        n, f = C.c_int64(), C.c_double()
-        _lib.check(_lib.lib().dv_penc_stats(self._h, C.byref(n), C.byref(f)), "dv_penc_stats")
-        return n.value, f.value
 
-    def probe(self, name):
-        """Named intermediate [B, L, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1 at prepare time)."""
-        dims = (C.c_int64 * 3)()
-        _lib.check(_lib.lib().dv_penc_probe(self._h, name.encode(), None, 0, dims), "dv_penc_probe")
-        out = torch.empty(tuple(dims), dtype=torch.float32)
-        _lib.check(_lib.lib().dv_penc_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims),
-                   "dv_penc_probe")
-        return out
-
-
-class TextEncoderEngine:
+class TextEncoderEngine(_NativeModule):
     """Native text encoder `enc_p` (dv_tenc_*, include/dvits_hip.h) for one mirror module (diff_vits_amd.model3.TextEncoder).
     Weights are synced like PromptEncoderEngine's (re-packed when a parameter's data_ptr / _version moves); the planned
     schedule is kept per (B, T): the handle holds one, a change of shape re-plans it (the packed weights survive)."""
+    _abi = "dv_tenc"
 
     def __init__(self, module):
-        self.module = module
         enc = module.encoder
         att = enc.attn_layers[0]
         c = _lib.TencCfg()
@@ -810,34 +848,7 @@ class TextEncoderEngine:
         c.gin_channels = enc.spk_emb_linear.in_features if hasattr(enc, "spk_emb_linear") else 0
         c.cond_layer_idx = enc.cond_layer_idx if c.gin_channels else 0
         self.cfg = c
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().dv_tenc_create(C.byref(c), C.byref(self._h)), "dv_tenc_create")
-        self._weight_sig = None
-        self._prepared = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                _lib.lib().dv_tenc_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def sync_weights(self):
-        m = self.module
-        sig = tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
-        if sig == self._weight_sig:
-            return
-        L = _lib.lib()
-        for name, t in m.state_dict().items():
-            if not t.is_cuda:
-                raise RuntimeError("backend='hip' needs the module on a GPU (parameter %s is on %s)" % (name, t.device))
-            t32 = t.detach().to(torch.float32).contiguous()
-            shape = (C.c_int64 * t32.dim())(*t32.shape)
-            _lib.check(L.dv_tenc_set_weight(self._h, name.encode(), _lib.ptr(t32), shape, t32.dim()), "dv_tenc_set_weight(%s)" % name)
-        torch.cuda.synchronize()
-        self._weight_sig = sig
-        self._prepared = None
+        self._create(module, c)
 
     def validate(self, ids, lengths, tone, language):
         """The host checks of the mirror (one device-to-host read): ValueError before anything is launched."""
@@ -863,13 +874,7 @@ class TextEncoderEngine:
             _lib.check(_lib.lib().dv_tenc_prepare(self._h, B, T, _lib.PREC_BF16X3), "dv_tenc_prepare")
             self._prepared = (B, T)
         c = self.cfg
-        gp = None
-        if g is not None:
-            if c.gin_channels == 0:
-                raise ValueError("this text encoder was built without speaker conditioning (gin_channels = 0)")
-            gp = g.detach().to(torch.float32).reshape(B, -1).contiguous()
-            if gp.shape[1] != c.gin_channels:
-                raise ValueError("g must hold %d channels per utterance, got %s" % (c.gin_channels, tuple(g.shape)))
+        gp = speaker_rows(g, B, c.gin_channels, "text encoder")
         ids, tone, language, lengths = (t.contiguous() for t in (ids, tone, language, lengths))
         x = torch.empty((B, c.hidden_channels, T), device=ids.device, dtype=torch.float32)
         stats = torch.empty((2, B, c.out_channels, T), device=ids.device, dtype=torch.float32)
@@ -877,62 +882,22 @@ class TextEncoderEngine:
                                               _lib.ptr(x), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.stream_ptr()), "dv_tenc_forward")
         return x, stats[0], stats[1]
 
-    def stats(self):
-        n, f = C.c_int64(), C.c_double()
-        _lib.check(_lib.lib().dv_tenc_stats(self._h, C.byref(n), C.byref(f)), "dv_tenc_stats")
-        return n.value, f.value
 
-    def probe(self, name):
-        """Named intermediate [B, T, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1 at prepare time)."""
-        dims = (C.c_int64 * 3)()
-        _lib.check(_lib.lib().dv_tenc_probe(self._h, name.encode(), None, 0, dims), "dv_tenc_probe")
-        out = torch.empty(tuple(dims), dtype=torch.float32)
-        _lib.check(_lib.lib().dv_tenc_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims), "dv_tenc_probe")
-        return out
-
-
-class PosteriorEncoderEngine:
+class PosteriorEncoderEngine(_NativeModule):
     """Native posterior encoder `enc_q` (dv_qenc_*, include/dvits_hip.h) for one mirror module
     (diff_vits_amd.model3.PosteriorEncoder): one k_wn_layer launch per WaveNet layer (csrc/kernels_wn.hip).  Weights are synced
     like TextEncoderEngine's (re-packed, weight norm folded, when a parameter's data_ptr / _version moves); the planned schedule
     is kept per (B, T): the handle holds one, a change of shape re-plans it (the packed weights survive)."""
+    _abi = "dv_qenc"
 
     def __init__(self, module):
-        self.module = module
         wn = module.enc
         c = _lib.QencCfg()
         c.in_channels, c.out_channels, c.hidden_channels = module.pre.in_channels, module.out_channels, wn.hidden_channels
         c.kernel_size, c.n_layers, c.gin_channels = wn.in_layers[0].kernel_size[0], wn.n_layers, wn.gin_channels
         c.dilation_rate = wn.in_layers[1].dilation[0] if wn.n_layers > 1 else 1
         self.cfg = c
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().dv_qenc_create(C.byref(c), C.byref(self._h)), "dv_qenc_create")
-        self._weight_sig = None
-        self._prepared = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                _lib.lib().dv_qenc_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def sync_weights(self):
-        m = self.module
-        sig = tuple((v.data_ptr(), v._version) for v in m.parameters()) + tuple((v.data_ptr(), v._version) for v in m.buffers())
-        if sig == self._weight_sig:
-            return
-        L = _lib.lib()
-        for name, t in m.state_dict().items():
-            if not t.is_cuda:
-                raise RuntimeError("backend='hip' needs the module on a GPU (parameter %s is on %s)" % (name, t.device))
-            t32 = t.detach().to(torch.float32).contiguous()
-            shape = (C.c_int64 * t32.dim())(*t32.shape)
-            _lib.check(L.dv_qenc_set_weight(self._h, name.encode(), _lib.ptr(t32), shape, t32.dim()), "dv_qenc_set_weight(%s)" % name)
-        torch.cuda.synchronize()
-        self._weight_sig = sig
-        self._prepared = None
+        self._create(module, c)
 
     def forward(self, y, lengths, g=None, noise=None):
         """y float [B, Cin, T], lengths int64 [B], g [B, gin] / [B, gin, 1] or None, noise [B, C, T] or None (drawn here with
@@ -951,13 +916,7 @@ class PosteriorEncoderEngine:
         if (B, T) != self._prepared:
             _lib.check(_lib.lib().dv_qenc_prepare(self._h, B, T, _lib.PREC_BF16X3), "dv_qenc_prepare")
             self._prepared = (B, T)
-        gp = None
-        if g is not None:
-            if c.gin_channels == 0:
-                raise ValueError("this posterior encoder was built without speaker conditioning (gin_channels = 0)")
-            gp = g.detach().to(torch.float32).reshape(B, -1).contiguous()
-            if gp.shape[1] != c.gin_channels:
-                raise ValueError("g must hold %d channels per utterance, got %s" % (c.gin_channels, tuple(g.shape)))
+        gp = speaker_rows(g, B, c.gin_channels, "posterior encoder")
         if noise is None:
             eps = torch.randn((B, c.out_channels, T), device=y.device, dtype=torch.float32)
         else:
@@ -971,24 +930,11 @@ class PosteriorEncoderEngine:
                                               _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream_ptr()), "dv_qenc_forward")
         return out[0], out[1], out[2]
 
-    def stats(self):
-        n, f = C.c_int64(), C.c_double()
-        _lib.check(_lib.lib().dv_qenc_stats(self._h, C.byref(n), C.byref(f)), "dv_qenc_stats")
-        return n.value, f.value
-
     def time_layers(self, reps=50):
         """Microseconds per pass of the n_layers k_wn_layer launches of the last forward, replayed `reps` times between two events."""
         us = C.c_float()
         _lib.check(_lib.lib().dv_qenc_time_layers(self._h, reps, _lib.stream_ptr(), C.byref(us)), "dv_qenc_time_layers")
         return us.value
-
-    def probe(self, name):
-        """Named intermediate [B, T, C] of the last forward (needs DVITS_KEEP_INTERMEDIATES=1 at prepare time)."""
-        dims = (C.c_int64 * 3)()
-        _lib.check(_lib.lib().dv_qenc_probe(self._h, name.encode(), None, 0, dims), "dv_qenc_probe")
-        out = torch.empty(tuple(dims), dtype=torch.float32)
-        _lib.check(_lib.lib().dv_qenc_probe(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims), "dv_qenc_probe")
-        return out
 
 
 def check_index_tensor(name, t, n, shape):

@@ -268,3 +268,33 @@ def test_sampler_option_errors_like_reference():
         dpm_solver.DPM_Solver(fn, ns, algorithm_type="dpmsolver++").sample(x, steps=4, t_end=0.0)
     with pytest.raises(ValueError):
         dpm_solver.DPM_Solver(fn, ns, algorithm_type="dpmsolver++").sample(x, steps=4, method="bogus")
+
+
+class _StubLib:
+    """Stands in for the native library: every call succeeds, every dv_*_set_weight is recorded."""
+
+    def __init__(self):
+        self.uploads = []
+
+    def __getattr__(self, name):
+        if name.endswith("_set_weight"):
+            return lambda handle, weight, *rest: self.uploads.append((name, weight)) or 0
+        return lambda *args: 0
+
+
+@pytest.mark.parametrize("kind", ["prompt", "text", "posterior"])
+def test_encoder_engines_refuse_a_cpu_module_before_any_upload(monkeypatch, kind):
+    """The shared upload helper keeps the engines' RuntimeError for a module that is not on a GPU, and raises it before the
+    first dv_*_set_weight."""
+    from diff_vits_amd import _lib, engine, model3
+    stub = _StubLib()
+    monkeypatch.setattr(_lib, "lib", lambda: stub)
+    if kind == "prompt":
+        eng = engine.PromptEncoderEngine(model3.PromptEncoder(100, 128, 128, 1, 0.2, backend="hip"))
+    elif kind == "text":
+        eng = engine.TextEncoderEngine(model3.TextEncoder(20, 16, 64, 64, 2, 2, 3, 0.0, backend="hip"))
+    else:
+        eng = engine.PosteriorEncoderEngine(model3.PosteriorEncoder(20, 16, 256, 5, 1, 2, gin_channels=32, backend="hip"))
+    with pytest.raises(RuntimeError, match=r"backend='hip' needs the module on a GPU \(parameter \S+ is on cpu\)$"):
+        eng.sync_weights()
+    assert stub.uploads == [] and eng._weight_sig is None
