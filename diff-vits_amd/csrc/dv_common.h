@@ -219,6 +219,12 @@ bool chain_ff_supported(const ChainFFParams& p, int precision);
 // exchange words the in-launch GroupNorm of k_chain_ff needs (gnx.groups / gnx.sk_c set), 0: not possible (see gemm_gnx_plan)
 int chain_ff_gnx_plan(const ChainFFParams& p, int n_cu);
 hipError_t launch_chain_ff(const ChainFFParams& p, int precision, hipStream_t st);
+// The cross-attention chain (ChainParams with xa_*, C = 128, one workgroup per row block) and the feed-forward tail of the same
+// block as ONE row-block launch (k_chain_xa_ff): what launch_chain2(c) followed by launch_chain_ff(f) computes, bit for bit, with
+// h3, its planes and its row partials kept in LDS.  c.out3_hi / out3_lo / rowstat3 and f.a_hi / a_lo / rowstat are not used;
+// c.out3 is optional (fp32 h3 for a tapped plan).
+bool chain_xa_ff_supported(const ChainParams& c, const ChainFFParams& f, int precision);
+hipError_t launch_chain_xa_ff(const ChainParams& c, const ChainFFParams& f, int precision, hipStream_t st);
 
 // Feed-forward tail of a transformer block at C = 256 / 384 / 512 as ONE launch (k_ff_split, kernels_ffsplit.hip; reference
 // attention.py:189-203, 206-255, 280-301 + transformer_1d.py:300-326).  As two GEMMs the block costs 55-62 us at the bench

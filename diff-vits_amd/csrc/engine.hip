@@ -773,6 +773,8 @@ struct Builder {
   }
   bool ff_split_on = [] { const char* e = getenv("DVITS_FF_SPLIT"); return !(e && e[0] == '0'); }();
   bool chain_ff_on = [] { const char* e = getenv("DVITS_CHAIN_FF"); return !(e && e[0] == '0'); }();
+  // C = 128 blocks: the cross-attention chain and the feed-forward chain as ONE launch (k_chain_xa_ff); 0: the two launches
+  bool chain_merge_ff128_on = [] { const char* e = getenv("DVITS_CHAIN_MERGE_FF128"); return !(e && e[0] == '0'); }();
   bool chain_split_on = [] { const char* e = getenv("DVITS_CHAIN_SPLIT"); return !(e && e[0] == '0'); }();
   bool chain_xsplit_on = [] { const char* e = getenv("DVITS_CHAIN_XSPLIT"); return !(e && e[0] == '0'); }();
   bool qkv_split_on = [] { const char* e = getenv("DVITS_QKV_SPLIT"); return !(e && e[0] == '0'); }();
@@ -1255,6 +1257,20 @@ struct Builder {
     return ao;
   }
 
+  // C = 128: the cross-attention chain (k_chain2<1, 0, true>) and the feed-forward chain (k_chain_ff) own the same 32 rows per
+  // workgroup, and nothing between them needs another workgroup: planned as ONE launch (k_chain_xa_ff, DVITS_CHAIN_MERGE_FF128=0:
+  // two) exactly where xf_xattn_chain would launch the row-block chain and xf_ff would launch k_chain_ff.  xf_tail leaves the
+  // chain's parameters and the tensors it consumes here, ff_launch emits the launch.
+  struct XaFF { bool set = false; ChainParams cp{}; double flops = 0.0; float* h = nullptr; Planes ao; float* h2 = nullptr; } xa_ff;
+  bool xa_ff128_ok(const Xf& b) const {
+    ChainFFParams cf{};
+    cf.M = b.M; cf.C = b.C; cf.T = b.Tp; cf.Tv = b.Tn;
+    const bool ff_one_launch = b.merged_ffproj && chain_on && !arena.exact && b.x.stat16 && chain_ff_on && chain_ff_supported(cf, prec);   // (xf_ff)
+    // (DVITS_QKV_XA_MIN_C=128 puts this width's cross-attention chain under DVITS_QKV_SPLIT's switch between the row-block chain and
+    // k_qkv_split MODE 2: it stays a launch of its own in both positions, so that the switch compares like with like)
+    const bool xa_switched = qkv_xa_on && b.C >= qkv_xa_min_c;
+    return chain_merge_ff128_on && b.C == 128 && ff_one_launch && !xa_switched;
+  }
   // The chained block's attention tail: to_out + residual h -> LN2 -> to_q, the cross attention (inside the launch, or after
   // it) -> to_out + residual -> h3 + LN3 partials l3.  Consumes h and the self attention's output ao.
   bool xf_tail(std::vector<OpFn>& ops, const Xf& b, float* h, Planes ao, float*& h3, LnIn& l3) {
@@ -1262,6 +1278,16 @@ struct Builder {
     if (xa_ok(b.Tp, C) && cross_frag.count(b.p)) {
       if (!frag(b.w_o2)) return false;
       float* h2 = alloc((size_t)M * C);
+      if (xa_ff128_ok(b)) {
+        // the chain is not launched here: xf_ff emits it with the feed-forward stages behind it (k_chain_xa_ff).  h3 stays in
+        // the workgroup - only a tapped plan asks for its fp32 rows
+        h3 = u->tap_mode ? alloc((size_t)M * C) : nullptr;
+        l3 = LnIn{};
+        xa_ff = XaFF{};
+        xa_ff.cp = xattn_chain_params(b, h, ao, h2, h3, l3, &xa_ff.flops);
+        xa_ff.h = h; xa_ff.ao = ao; xa_ff.h2 = h2; xa_ff.set = true;
+        return true;
+      }
       h3 = alloc((size_t)M * C);
       l3 = ln_planes(M, C);
       xf_xattn_chain(ops, b, h, ao, h2, h3, l3);
@@ -1310,8 +1336,9 @@ struct Builder {
   }
   // chain 2 with the cross attention inside: to_out + residual -> LN2 -> to_q -> cross attention (wave = head, K / V
   // of the prompt as hoisted MFMA fragments) -> to_out + residual -> LN3 partials   (4 launches -> 1)
-  void xf_xattn_chain(std::vector<OpFn>& ops, const Xf& b, float* h, Planes ao, float* h2, float* h3, const LnIn& l3) {
-    const int C = b.C, Tp = b.Tp, M = b.M;
+  // the launch's parameters with one workgroup per row block; *flops: the attention and stage 3 (beyond chain_flops)
+  ChainParams xattn_chain_params(const Xf& b, float* h, Planes ao, float* h2, float* h3, const LnIn& l3, double* flops) {
+    const int C = b.C;
     const XFrag& xf = cross_frag[b.p];
     ChainParams cp = tail_chain(b, h, ao, h2);
     cp.xa_kf_hi = xf.kf_hi; cp.xa_kf_lo = xf.kf_lo; cp.xa_vf_hi = xf.vf_hi; cp.xa_vf_lo = xf.vf_lo; cp.xa_bias = xbias;
@@ -1319,6 +1346,13 @@ struct Builder {
     cp.xa_qscale = (1.0f / sqrtf((float)cp.xa_d)) * 1.44269504088896340736f;
     cp.w3_hi = b.w_o2->fhi; cp.w3_lo = b.w_o2->flo; cp.b3 = b.w_o2->bias;
     cp.out3 = h3; cp.out3_hi = l3.pl.hi; cp.out3_lo = l3.pl.lo; cp.rowstat3 = l3.stat;
+    *flops = 4.0 * B * u->cfg.num_heads * (double)b.Tp * L * cp.xa_d + 2.0 * (double)b.M * C * C;
+    return cp;
+  }
+  void xf_xattn_chain(std::vector<OpFn>& ops, const Xf& b, float* h, Planes ao, float* h2, float* h3, const LnIn& l3) {
+    const int C = b.C, Tp = b.Tp, M = b.M;
+    double xattn_flops = 0.0;
+    ChainParams cp = xattn_chain_params(b, h, ao, h2, h3, l3, &xattn_flops);
     {   // C = 256 with few row blocks (M = 4096 at the bench shape: 128 for 256 CUs): two workgroups per row block, heads
         // 0-3 / 4-7, two waves per head, stage 3 handed over like a fused split-K pair (DVITS_CHAIN_XSPLIT=0: one)
       const int rbs = M / 32, cus = n_cu > 0 ? n_cu : 256;
@@ -1333,7 +1367,6 @@ struct Builder {
     // row blocks (DVITS_QKV_XA=0: the row-block chain above)
     ChainParams cq = cp;
     cq.nsplit = 1; cq.xs_buf = nullptr; cq.xs_ticket = nullptr;
-    const double xattn_flops = 4.0 * B * u->cfg.num_heads * (double)Tp * L * cp.xa_d + 2.0 * (double)M * C * C;
     const int n_wg = (M / 64) * (C / 64);
     bool split_xa = qkv_split_on && qkv_xa_on && C >= qkv_xa_min_c && handover_ok() && !autotune_on() &&
                     Tp % 64 == 0 && (M / 64) % 8 == 0 && n_wg <= n_cu && n_wg >= qkv_split_min_wg && u->cfg.num_heads == 8 &&
@@ -1440,7 +1473,7 @@ struct Builder {
     fs.rows = ff_split_rows(C, M, Tp, fs.nspl, n_cu);   // 64 rows per workgroup; 32 at C = 512, odd pitches, small inputs
     const int ff_wg = (M / fs.rows) * fs.nspl;
     const size_t n_flags = (size_t)ff_wg * 8;         // one word per wave (kernels_ffsplit.hip)
-    if (one_launch && chain_ff_on && chain_ff_supported(cf, prec)) return ff_launch(ops, b, cf, h3, l3, want_planes);
+    if (xa_ff.set || (one_launch && chain_ff_on && chain_ff_supported(cf, prec))) return ff_launch(ops, b, cf, h3, l3, want_planes);
     else if (one_launch && ff_split_on && handover_ok() && !autotune_on() && (C == 256 || C == 384 || C == 512) &&
              ff_split_supported(fs, prec) && (ff_wg <= n_cu || gemm_handover_rounds()) && ff_wg >= ff_split_min_wg &&
              gnx_used + n_flags <= dv_unet::GNX_POOL)
@@ -1490,6 +1523,22 @@ struct Builder {
       emit_launch(ops, "chain", flops, strf("LN+GEGLU+ffproj+res%s (%d wg / %d rows) M=%d C=%d", gnx, fp.nspl, fp.rows, M, C),
                   [fp, pr](hipStream_t st) { return launch_ff_split(fp, pr, st); });
       release(fp.xbuf);
+    } else if (xa_ff.set) {
+      // (the description keeps k_chain_ff's head: the launch is counted wherever that one is)
+      const XaFF x = xa_ff;
+      xa_ff = XaFF{};
+      const ChainParams cp = x.cp;
+      // (the planning pass holds no fragment-major weights yet: the check needs the real pass's pointers; launch_chain_xa_ff repeats it)
+      if (!dry && !chain_xa_ff_supported(cp, fp, pr)) { err ="the merged C = 128 chain refused a shape its planner admitted"; return Act{}; }
+      emit_launch(ops, "chain", chain_flops(cp) + x.flops + flops,
+                  strf("LN+GEGLU+ffproj+res%s after to_out+res+LN+to_q+xattn+to_out+res M=%d C=%d", gnx, M, C),
+                  [cp, fp, pr](hipStream_t st) { return launch_chain_xa_ff(cp, fp, pr, st); });
+      release(x.ao); release(x.h);
+      probe(b.tb + "attn1", x.h2, b.Tn, C);
+      release(x.h2);
+      if (h3) { probe(b.tb + "attn2", h3, b.Tn, C); release(h3); }
+      probe(b.p.substr(0, b.p.size() - 1), out);
+      return out;
     } else {
       emit_launch(ops, "chain", flops, strf("LN+GEGLU+ffproj+res%s M=%d C=%d", gnx, M, C),
                   [fp, pr](hipStream_t st) { return launch_chain_ff(fp, pr, st); });

@@ -78,8 +78,20 @@ constexpr bool chain_pf_wave() {
   return NS == 1 || (NS == 2 && AMODE == 0);
 }
 
-template <int NS, int AMODE, bool XA = false, bool SA = false, bool CS = false>
-__global__ __launch_bounds__((chain_pf_wave<NS, AMODE, XA, SA, CS>() ? NT_LAUNCH : NT)) void k_chain2(const ChainParams p) {
+// The feed-forward stages of a C = 128 block (defined with k_chain_ff below): k_chain_ff runs them on h3 planes and row
+// partials it fetches from global memory, k_chain_xa_ff behind the cross-attention chain on what its stage 3 left in LDS
+struct WFrag { bf16x8 h, l; };                     // one weight fragment: its two operand planes
+__device__ __forceinline__ void ff_l2_prefetch(const ChainFFParams& p, unsigned pf_lds, int w, int nw);
+__device__ __forceinline__ WFrag ff_load_a_unit(const ChainFFParams& p, int U, int wave, int lane);
+__device__ __forceinline__ float2 ff_ln_row(const float2 (&v)[4], float ln_eps);
+__device__ __forceinline__ void chain_ff_stages(const ChainFFParams& p, char* a_reg, char* g_reg, char* red_reg, float2 st,
+                                                WFrag (&bq)[DEPTH_FF], int tid);
+struct ChainXaFFParams : ChainParams { ChainFFParams ff; };
+
+// FF (k_chain_xa_ff: NS = 1, XA): stage 3 leaves h3 in LDS - raw split planes in the A region, LayerNorm row partials in
+// s_rowp - and the workgroup goes on with the feed-forward stages (p.ff); h3 reaches global memory only where p.out3 is set
+template <int NS, int AMODE, bool XA, bool SA, bool CS, bool FF, class P>
+__device__ __forceinline__ void chain2_body(const P& p) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   constexpr int CH = 2 * NS;                       // 64-channel chunks of the A operand
   constexpr int A_PL = CH * CHUNK_PL;              // bytes per plane of the resident A operand
@@ -269,6 +281,9 @@ __global__ __launch_bounds__((chain_pf_wave<NS, AMODE, XA, SA, CS>() ? NT_LAUNCH
   BFrag bq[DEPTH];
   stage_prologue(p.w1_hi, p.w1_lo, 0, bq, std::integral_constant<int, NS>{}, KHfull{}, 0);   // the first weight fragments fly under the A operand's arrival / conversion
   if (!PFW && !XA && DV_CHAIN_PFMODE == 2) l2_prefetch(wave, NWV);   // (XA kernels: measured +-0 with it, round 4)
+  // (the feed-forward stages' weights - four times the chain's - are what k_chain_ff's ninth wave requests: here the eight
+  // compute waves share the requests out, a whole chain ahead of their first use)
+  if constexpr (FF) ff_l2_prefetch(p.ff, (unsigned)(size_t)s_pf, wave, NWV);
   if (AMODE == 1) {
     // GroupNorm of the fp32 rows, once per row-block: table of this utterance, then convert
     const int T = p.T, b_item = m0 / T, Tv = p.Tv > 0 ? p.Tv : T;   // row pitch / frames that exist (padded row spaces)
@@ -706,7 +721,15 @@ __global__ __launch_bounds__((chain_pf_wave<NS, AMODE, XA, SA, CS>() ? NT_LAUNCH
       for (int r = 0; r < 16; ++r) acc[ns][r] = 0.f;
     stage_loop(p.w3_hi, p.w3_lo, 0, bq, acc, std::false_type{}, std::integral_constant<int, NS>{}, KH3{}, ks3);
     DV_CTRACE(13);
-    kgroup_reduce(acc, red_reg, OwnNone{});
+    // FF: the GEGLU weights' first fragments depend on nothing this launch computes - in flight under the hand-over and
+    // the epilogue, in all eight waves
+    [[maybe_unused]] WFrag fq[FF ? DEPTH_FF : 1];
+    if constexpr (FF) {
+#pragma unroll
+      for (int j = 0; j < DEPTH_FF; ++j) fq[j] = ff_load_a_unit(p.ff, j, wave, lane);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    kgroup_reduce(acc, red_reg, OwnNone{});          // (its leading barrier: every wave is done reading the attention output)
     DV_CTRACE(14);
     if (XS) {
       // hand-over between the two workgroups of the row block (the fused split-K pair's protocol, gemm_tile.h): dump the
@@ -754,11 +777,30 @@ __global__ __launch_bounds__((chain_pf_wave<NS, AMODE, XA, SA, CS>() ? NT_LAUNCH
           vv[4 * g] = acc[ns][4 * g] + bv.x + rr.x; vv[4 * g + 1] = acc[ns][4 * g + 1] + bv.y + rr.y;
           vv[4 * g + 2] = acc[ns][4 * g + 2] + bv.z + rr.z; vv[4 * g + 3] = acc[ns][4 * g + 3] + bv.w + rr.w;
         }
+        if (!FF || p.out3) {                           // (FF: only a tapped plan reads h3)
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-          dv_st16(p.out3 + (size_t)m * C + nf + 8 * g, make_float4(vv[4 * g], vv[4 * g + 1], vv[4 * g + 2], vv[4 * g + 3]));
-        // split planes as 16-byte stores (lane pairs exchange halves: dv_device.h store_planes16)
-        store_planes16(p.out3_hi, p.out3_lo, (size_t)m * C + nf - 4 * lh, lh, vv);
+          for (int g = 0; g < 4; ++g)
+            dv_st16(p.out3 + (size_t)m * C + nf + 8 * g, make_float4(vv[4 * g], vv[4 * g + 1], vv[4 * g + 2], vv[4 * g + 3]));
+        }
+        if constexpr (FF) {
+          // the raw planes stay here, in the A region (the attention output is dead), as epilogue 1 leaves x1: the roundings
+          // of store_planes16
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int n = nf + 8 * g;
+            uint2 hw, lw;
+            hw.x = pk(vv[4 * g], vv[4 * g + 1]); hw.y = pk(vv[4 * g + 2], vv[4 * g + 3]);
+            lw.x = pk(vv[4 * g] - __uint_as_float(hw.x << 16), vv[4 * g + 1] - __uint_as_float(hw.x & 0xffff0000u));
+            lw.y = pk(vv[4 * g + 2] - __uint_as_float(hw.y << 16), vv[4 * g + 3] - __uint_as_float(hw.y & 0xffff0000u));
+            const int c = n >> 6, s16 = (n & 63) >> 3;
+            const int off = c * CHUNK_PL + l31 * 128 + ((s16 ^ swz(l31)) << 4) + ((n & 7) >> 2) * 8;
+            *reinterpret_cast<uint2*>(a_reg + off) = hw;
+            *reinterpret_cast<uint2*>(a_reg + A_PL + off) = lw;
+          }
+        } else {
+          // split planes as 16-byte stores (lane pairs exchange halves: dv_device.h store_planes16)
+          store_planes16(p.out3_hi, p.out3_lo, (size_t)m * C + nf - 4 * lh, lh, vv);
+        }
         float a = 0.f, q = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) a += vv[r];
@@ -767,12 +809,33 @@ __global__ __launch_bounds__((chain_pf_wave<NS, AMODE, XA, SA, CS>() ? NT_LAUNCH
 #pragma unroll
         for (int r = 0; r < 16; ++r) q += (vv[r] - mb) * (vv[r] - mb);
         q = pair_sum32(q);
-        if (lh == 0) reinterpret_cast<float2*>(p.rowstat3)[(size_t)m * (C / 32) + ns * 4 + wn] = make_float2(a, q);
+        if (lh == 0) {
+          if constexpr (FF) s_rowp[l31][ns * 4 + wn] = make_float2(a, q);
+          else reinterpret_cast<float2*>(p.rowstat3)[(size_t)m * (C / 32) + ns * 4 + wn] = make_float2(a, q);
+        }
       }
+    }
+    if constexpr (FF) {
+      // ================= LN3 -> GEGLU -> merged ff.net.2 + proj_out + residual: k_chain_ff's stages on the resident h3 =================
+      // LDS: [h3 planes 16 KiB | GEGLU product 64 KiB (its head was the chain's hand-over region) | hand-over 16 KiB]
+      __syncthreads();                             // planes and row partials of h3 are visible; the hand-over region is free
+      DV_CTRACE(15);
+      float2 v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = s_rowp[l31][k];
+      chain_ff_stages(p.ff, a_reg, red_reg, red_reg + 2 * 8 * CHUNK_PL, ff_ln_row(v, p.ff.ln_eps), fq, tid);
     }
   }
   DV_CTRACE(9);
 }
+
+template <int NS, int AMODE, bool XA = false, bool SA = false, bool CS = false>
+__global__ __launch_bounds__((chain_pf_wave<NS, AMODE, XA, SA, CS>() ? NT_LAUNCH : NT)) void k_chain2(const ChainParams p) {
+  chain2_body<NS, AMODE, XA, SA, CS, false>(p);
+}
+// attention output -> ... -> attn2.to_out + residual (k_chain2<1, 0, true>) -> LN3 -> GEGLU -> merged ffproj + residual
+// (k_chain_ff) of a C = 128 block as one launch: eight waves with the full 256 VGPRs, no ninth wave
+__global__ __launch_bounds__(NT) void k_chain_xa_ff(const ChainXaFFParams p) { chain2_body<1, 0, true, false, false, true>(p); }
 
 // ---------------------------------------------------------------------------------------
 // k_chain_ff (ChainFFParams): LN3 -> GEGLU -> merged ff.net.2 + proj_out + residual of a C = 128 transformer block as one
@@ -784,81 +847,66 @@ __global__ __launch_bounds__((chain_pf_wave<NS, AMODE, XA, SA, CS>() ? NT_LAUNCH
 //   stage B: 4 column-fragment owners x 2 k-groups over K = 5C = [h3 planes | product planes], then bias + residual,
 //            fp32 rows + 32x16 block statistics for the next GroupNorm
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT_LAUNCH) void k_chain_ff(const ChainFFParams p) {
-  extern __shared__ __attribute__((aligned(1024))) char smem[];
+// L2 prefetch of the feed-forward weights, this workgroup's residual rows and the GEGLU bias / u vectors (see k_chain2's
+// l2_prefetch), by wave w of the nw that share it out: k_chain_ff's ninth wave, or the compute waves of k_chain_xa_ff
+__device__ __forceinline__ void ff_l2_prefetch(const ChainFFParams& p, unsigned pf_lds, int w, int nw) {
+  constexpr int C = 128;
+  const int lane = threadIdx.x & 63;
+  const int xw = blockIdx.x >> 3, nxw = (gridDim.x + 7) >> 3;
+  const int lg = 8 * C * C / 64, lm = 5 * C * C / 64;        // 128-byte lines per plane
+  const int total = 2 * (lg + lm), per = (total + nxw - 1) / nxw, end = min(total, (xw + 1) * per);
+  for (int ln = xw * per + w * 64 + lane; ln < end; ln += 64 * nw) {
+    const char* src;
+    if (ln < lg) src = reinterpret_cast<const char*>(p.wg_hi) + (size_t)ln * 128;
+    else if (ln < 2 * lg) src = reinterpret_cast<const char*>(p.wg_lo) + (size_t)(ln - lg) * 128;
+    else if (ln < 2 * lg + lm) src = reinterpret_cast<const char*>(p.wm_hi) + (size_t)(ln - 2 * lg) * 128;
+    else src = reinterpret_cast<const char*>(p.wm_lo) + (size_t)(ln - 2 * lg - lm) * 128;
+    glds4(src, pf_lds);
+  }
+  const char* r0 = reinterpret_cast<const char*>(p.res + (size_t)blockIdx.x * BM * C);
+  for (int ln = w * 64 + lane; ln < BM * C / 32; ln += 64 * nw) glds4(r0 + (size_t)ln * 128, pf_lds);
+  if (w == 0) {
+    for (int ln = lane; ln < 8 * C / 32; ln += 64) {
+      glds4(reinterpret_cast<const char*>(p.bg) + (size_t)ln * 128, pf_lds);
+      glds4(reinterpret_cast<const char*>(p.ug) + (size_t)ln * 128, pf_lds);
+    }
+  }
+}
+// stage A weights: unit U = pass * 16 + ks * 2 + f  (f: 0 = the `a` fragment, 1 = the gate fragment of this wave's block)
+__device__ __forceinline__ WFrag ff_load_a_unit(const ChainFFParams& p, int U, int wave, int lane) {
+  const int nf = 2 * ((U >> 4) * 8 + wave) + (U & 1), ks = (U & 15) >> 1;
+  const size_t e = ((size_t)(nf * 8 + ks) * 64 + lane) * 8;
+  WFrag f;
+  f.h = *reinterpret_cast<const bf16x8*>(p.wg_hi + e);
+  f.l = *reinterpret_cast<const bf16x8*>(p.wg_lo + e);
+  return f;
+}
+// LayerNorm (mean, rstd) of one row of h3 from its four 32-column partials (sum, M2 about the block mean)
+__device__ __forceinline__ float2 ff_ln_row(const float2 (&v)[4], float ln_eps) {
+  constexpr int C = 128;
+  float s1 = 0.f;
+#pragma unroll
+  for (int k = 0; k < C / 32; ++k) s1 += v[k].x;
+  const float inv_c = 1.0f / (float)C, mean = s1 * inv_c;
+  float m2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < C / 32; ++k) { const float dm = v[k].x * (1.0f / 32.0f) - mean; m2 += v[k].y + 32.0f * dm * dm; }
+  return make_float2(mean, 1.0f / sqrtf(m2 * inv_c + ln_eps));
+}
+
+// Stage A, stage B and the epilogue.  Entered by the eight compute waves behind a barrier: the raw planes of h3 are in a_reg
+// ([2 planes][2 chunks][32 rows][128 B]), st = this lane's row's (mean, rstd), bq = the first DEPTH_FF stage-A weight units.
+// g_reg ([2 planes][8 chunks][32 rows][128 B]) receives the product, red_reg (16 KiB) the k-group hand-over.
+__device__ __forceinline__ void chain_ff_stages(const ChainFFParams& p, char* const a_reg, char* const g_reg, char* const red_reg,
+                                                const float2 st, WFrag (&bq)[DEPTH_FF], const int tid) {
   constexpr int C = 128, A_CH = 2, G_CH = 8;                 // 64-channel chunks of h3 / of the GEGLU product
   constexpr int A_PL = A_CH * CHUNK_PL, G_PL = G_CH * CHUNK_PL;
-  char* const a_reg = smem;                                  // [2 planes][2 chunks][32 rows][128 B]
-  char* const g_reg = smem + 2 * A_PL;                       // [2 planes][8 chunks][32 rows][128 B]
-  char* const red_reg = g_reg + 2 * G_PL;                    // 16 KiB k-group hand-over
-  __shared__ __attribute__((aligned(16))) float2 s_ln[BM];
-  asm volatile("" ::"s"(p.M), "s"(p.rowstat), "s"(p.wg_lo), "s"(p.wm_hi), "s"(p.res), "s"(p.out_lo));
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (wave == NWV) {                                         // ninth wave: L2 prefetch of the weight planes (see k_chain2)
-    __shared__ __attribute__((aligned(256))) unsigned s_pf[64];
-    const int xw = blockIdx.x >> 3, nxw = (gridDim.x + 7) >> 3;
-    const int lg = 8 * C * C / 64, lm = 5 * C * C / 64;      // 128-byte lines per plane
-    const int total = 2 * (lg + lm), per = (total + nxw - 1) / nxw, end = min(total, (xw + 1) * per);
-    for (int ln = xw * per + lane; ln < end; ln += 64) {
-      const char* src;
-      if (ln < lg) src = reinterpret_cast<const char*>(p.wg_hi) + (size_t)ln * 128;
-      else if (ln < 2 * lg) src = reinterpret_cast<const char*>(p.wg_lo) + (size_t)(ln - lg) * 128;
-      else if (ln < 2 * lg + lm) src = reinterpret_cast<const char*>(p.wm_hi) + (size_t)(ln - 2 * lg) * 128;
-      else src = reinterpret_cast<const char*>(p.wm_lo) + (size_t)(ln - 2 * lg - lm) * 128;
-      glds4(src, (unsigned)(size_t)s_pf);
-    }
-    const char* r0 = reinterpret_cast<const char*>(p.res + (size_t)blockIdx.x * BM * C);
-    for (int ln = lane; ln < BM * C / 32; ln += 64) glds4(r0 + (size_t)ln * 128, (unsigned)(size_t)s_pf);
-    for (int ln = lane; ln < 8 * C / 32; ln += 64) {
-      glds4(reinterpret_cast<const char*>(p.bg) + (size_t)ln * 128, (unsigned)(size_t)s_pf);
-      glds4(reinterpret_cast<const char*>(p.ug) + (size_t)ln * 128, (unsigned)(size_t)s_pf);
-    }
-    return;
-  }
+  using BFrag = WFrag;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * BM;
-  const unsigned a_base = (unsigned)(size_t)a_reg;
-  const int d_row = lane >> 3, d_slot = lane & 7;
-  struct BFrag { bf16x8 h, l; };
-
-  // ---- h3 planes -> LDS (LDS-DMA), LayerNorm row statistics from the producer's partials ----
-  for (int idx = wave; idx < A_CH * 4; idx += NWV) {
-    const int c = idx >> 2, r8 = idx & 3, row = r8 * 8 + d_row;
-    const size_t e = (size_t)(m0 + row) * C + c * 64 + ((d_slot ^ swz(row)) << 3);
-    const unsigned dst = a_base + (unsigned)(c * CHUNK_PL + r8 * 1024);
-    glds16(p.a_hi + e, dst);
-    glds16(p.a_lo + e, dst + A_PL);
-  }
-  // stage A weights: unit U = pass * 16 + ks * 2 + f  (f: 0 = the `a` fragment, 1 = the gate fragment of this wave's block)
   constexpr int UA = 32;
-  auto load_a_unit = [&](int U) __attribute__((always_inline)) {
-    const int nf = 2 * ((U >> 4) * 8 + wave) + (U & 1), ks = (U & 15) >> 1;
-    const size_t e = ((size_t)(nf * 8 + ks) * 64 + lane) * 8;
-    BFrag f;
-    f.h = *reinterpret_cast<const bf16x8*>(p.wg_hi + e);
-    f.l = *reinterpret_cast<const bf16x8*>(p.wg_lo + e);
-    return f;
-  };
-  BFrag bq[DEPTH_FF];
-#pragma unroll
-  for (int j = 0; j < DEPTH_FF; ++j) bq[j] = load_a_unit(j);
-  __builtin_amdgcn_sched_barrier(0);
-  if (tid < BM) {
-    const float2* src = reinterpret_cast<const float2*>(p.rowstat) + (size_t)(m0 + tid) * (C / 32);
-    float2 v[C / 32];
-#pragma unroll
-    for (int k = 0; k < C / 32; ++k) v[k] = src[k];
-    float s1 = 0.f;
-#pragma unroll
-    for (int k = 0; k < C / 32; ++k) s1 += v[k].x;
-    const float inv_c = 1.0f / (float)C, mean = s1 * inv_c;
-    float m2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < C / 32; ++k) { const float dm = v[k].x * (1.0f / 32.0f) - mean; m2 += v[k].y + 32.0f * dm * dm; }
-    s_ln[tid] = make_float2(mean, 1.0f / sqrtf(m2 * inv_c + p.ln_eps));
-  }
-  wait_vmcnt<0>();
-  __syncthreads();
+  auto load_a_unit = [&](int U) __attribute__((always_inline)) { return ff_load_a_unit(p, U, wave, lane); };
 
   // ================= stage A: GEGLU =================
   {
@@ -868,7 +916,6 @@ __global__ __launch_bounds__(NT_LAUNCH) void k_chain_ff(const ChainFFParams p) {
       h = *reinterpret_cast<const bf16x8*>(a_reg + off);
       l = *reinterpret_cast<const bf16x8*>(a_reg + A_PL + off);
     };
-    const float2 st = s_ln[l31];
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps) {
       f32x16 acc[2];
@@ -1043,6 +1090,49 @@ __global__ __launch_bounds__(NT_LAUNCH) void k_chain_ff(const ChainFFParams p) {
   }
 }
 
+__global__ __launch_bounds__(NT_LAUNCH) void k_chain_ff(const ChainFFParams p) {
+  extern __shared__ __attribute__((aligned(1024))) char smem[];
+  constexpr int C = 128, A_CH = 2, G_CH = 8;
+  constexpr int A_PL = A_CH * CHUNK_PL, G_PL = G_CH * CHUNK_PL;
+  char* const a_reg = smem;                                  // [2 planes][2 chunks][32 rows][128 B]
+  char* const g_reg = smem + 2 * A_PL;                       // [2 planes][8 chunks][32 rows][128 B]
+  char* const red_reg = g_reg + 2 * G_PL;                    // 16 KiB k-group hand-over
+  __shared__ __attribute__((aligned(16))) float2 s_ln[BM];
+  asm volatile("" ::"s"(p.M), "s"(p.rowstat), "s"(p.wg_lo), "s"(p.wm_hi), "s"(p.res), "s"(p.out_lo));
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (wave == NWV) {                                         // ninth wave: L2 prefetch of the weight planes (see k_chain2)
+    __shared__ __attribute__((aligned(256))) unsigned s_pf[64];
+    ff_l2_prefetch(p, (unsigned)(size_t)s_pf, 0, 1);
+    return;
+  }
+  const int m0 = blockIdx.x * BM;
+  const unsigned a_base = (unsigned)(size_t)a_reg;
+  const int d_row = lane >> 3, d_slot = lane & 7;
+
+  // ---- h3 planes -> LDS (LDS-DMA), LayerNorm row statistics from the producer's partials ----
+  for (int idx = wave; idx < A_CH * 4; idx += NWV) {
+    const int c = idx >> 2, r8 = idx & 3, row = r8 * 8 + d_row;
+    const size_t e = (size_t)(m0 + row) * C + c * 64 + ((d_slot ^ swz(row)) << 3);
+    const unsigned dst = a_base + (unsigned)(c * CHUNK_PL + r8 * 1024);
+    glds16(p.a_hi + e, dst);
+    glds16(p.a_lo + e, dst + A_PL);
+  }
+  WFrag bq[DEPTH_FF];
+#pragma unroll
+  for (int j = 0; j < DEPTH_FF; ++j) bq[j] = ff_load_a_unit(p, j, wave, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  if (tid < BM) {
+    const float2* src = reinterpret_cast<const float2*>(p.rowstat) + (size_t)(m0 + tid) * (C / 32);
+    float2 v[C / 32];
+#pragma unroll
+    for (int k = 0; k < C / 32; ++k) v[k] = src[k];
+    s_ln[tid] = ff_ln_row(v, p.ln_eps);
+  }
+  wait_vmcnt<0>();
+  __syncthreads();
+  chain_ff_stages(p, a_reg, g_reg, red_reg, s_ln[lane & 31], bq, tid);
+}
+
 // cross-attention K / V of one block, fp32 rows [B*L, 2C] (k | v), head h = columns [h*d, h*d + d) -> split-bf16 MFMA
 // fragments: K fragment (tile t, k-step ks): lane (l31, lh) = K[key t*32 + l31][ks*16 + lh*8 .. +8];  V^T fragment (tile t,
 // k-block kb, channel block nb): lane (l31, lh) = V[key(j)][nb*32 + l31], j = 0..7, key(j) = t*32 + kb*16 + (j < 4 ? 4 lh + j :
@@ -1137,23 +1227,47 @@ int chain_ff_gnx_plan(const ChainFFParams& p, int n_cu) {
   if (cpg % 16 != 0 || (p.T / 32) * (cpg / 16) > 256 || (gemm_handover_rounds() ? p.T / 32 : p.M / 32) > n_cu) return 0;
   return (p.M / 32) * (p.C / 16);
 }
-hipError_t launch_chain_ff(const ChainFFParams& p, int precision, hipStream_t st) {
-  if (!chain_ff_supported(p, precision)) return hipErrorInvalidValue;
-  if (!p.a_hi || !p.a_lo || !p.rowstat || !p.wg_hi || !p.wg_lo || !p.bg || !p.ug || !p.wm_hi || !p.wm_lo || !p.bm || !p.res ||
-      (p.out_hi && !p.out_lo))
-    return hipErrorInvalidValue;
+// what both launches of the feed-forward stages ask of their arguments (h3_global: the planes and row partials of h3 are read
+// from global memory - k_chain_ff)
+static bool chain_ff_args_ok(const ChainFFParams& p, int precision, bool h3_global) {
+  if (!chain_ff_supported(p, precision)) return false;
+  if (h3_global && (!p.a_hi || !p.a_lo || !p.rowstat)) return false;
+  if (!p.wg_hi || !p.wg_lo || !p.bg || !p.ug || !p.wm_hi || !p.wm_lo || !p.bm || !p.res || (p.out_hi && !p.out_lo)) return false;
   if (p.gnx.xchg) {
     static const int n_cu = [] { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
-    if (!p.gnx.status || !p.gnx.y_hi || !p.gnx.y_lo || !p.gnx.gamma || !p.gnx.beta || chain_ff_gnx_plan(p, n_cu) <= 0) return hipErrorInvalidValue;
-    if (p.gnx.sk_c > 0 && (!p.gnx.sk_x || !p.gnx.sk_stat16 || !p.gnx.sk_y_hi || !p.gnx.sk_y_lo)) return hipErrorInvalidValue;
-  } else if (!p.out) return hipErrorInvalidValue;
+    if (!p.gnx.status || !p.gnx.y_hi || !p.gnx.y_lo || !p.gnx.gamma || !p.gnx.beta || chain_ff_gnx_plan(p, n_cu) <= 0) return false;
+    if (p.gnx.sk_c > 0 && (!p.gnx.sk_x || !p.gnx.sk_stat16 || !p.gnx.sk_y_hi || !p.gnx.sk_y_lo)) return false;
+  } else if (!p.out) return false;
+  return true;
+}
+hipError_t launch_chain_ff(const ChainFFParams& p, int precision, hipStream_t st) {
+  if (!chain_ff_args_ok(p, precision, true)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_chain_ff, dim3(p.M / BM), dim3(NT_LAUNCH), FF_SMEM, st, p);
+  return hipGetLastError();
+}
+
+// k_chain_xa_ff: the cross-attention chain (c: amode 0, one pass, one workgroup per row block) and the feed-forward stages (f)
+// of the same C = 128 rows.  LDS: the chain's A region and hand-over region lie inside the feed-forward's layout (FF_SMEM).
+bool chain_xa_ff_supported(const ChainParams& c, const ChainFFParams& f, int precision) {
+  if (c.C != 128 || !c.xa_kf_hi || c.nsplit > 1 || c.sa_kf_hi || f.M != c.M || f.C != c.C || f.T != c.T || f.Tv != c.Tv) return false;
+  ChainParams t = c;                                 // (h3, its planes and its row partials stay in the workgroup: stage 3 needs no global ones)
+  t.out3 = c.out1; t.out3_hi = t.out3_lo = reinterpret_cast<bf16_t*>(c.out1); t.rowstat3 = c.out1;
+  return chain2_supported(t, precision) && chain_ff_supported(f, precision);
+}
+hipError_t launch_chain_xa_ff(const ChainParams& c, const ChainFFParams& f, int precision, hipStream_t st) {
+  if (!chain_xa_ff_supported(c, f, precision) || !chain_ff_args_ok(f, precision, false)) return hipErrorInvalidValue;
+  if (!c.a_hi || !c.a_lo || !c.w1_hi || !c.w1_lo || !c.w2_hi || !c.w2_lo || !c.b1 || !c.b2 || !c.u2 || !c.out1) return hipErrorInvalidValue;
+  ChainXaFFParams p;
+  static_cast<ChainParams&>(p) = c;
+  p.ff = f;
+  hipLaunchKernelGGL(k_chain_xa_ff, dim3(c.M / BM), dim3(NT), FF_SMEM, st, p);
   return hipGetLastError();
 }
 
 hipError_t chain_init() {
   hipError_t e;
   if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain_ff), hipFuncAttributeMaxDynamicSharedMemorySize, FF_SMEM)) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain_xa_ff), hipFuncAttributeMaxDynamicSharedMemorySize, FF_SMEM)) != hipSuccess) return e;
   if ((e = init_one<1, 0>()) != hipSuccess) return e;
   if ((e = init_one<2, 0>()) != hipSuccess) return e;
   if ((e = init_one<3, 0>()) != hipSuccess) return e;
