@@ -51,6 +51,8 @@ MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, 
 SIGNATURES = {
     "dv_last_error": (C.c_char_p, []),
     "dv_version": (C.c_char_p, []),
+    "dv_poisoned_bytes": (C.c_int64, []),
+    "dv_unwritten_bytes": (C.c_int64, []),
     "dv_unet_create": (C.c_int, [C.POINTER(UNetCfg), C.POINTER(C.c_void_p)]),
     "dv_unet_destroy": (None, [C.c_void_p]),
     "dv_unet_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),

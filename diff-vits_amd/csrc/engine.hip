@@ -38,6 +38,8 @@ extern "C" const char* dv_last_error(void) { return g_err; }
 // the build identity: profiles/*_pmc_roofline.json is stamped with it and bench.py reports those figures only while it
 // still is the loaded library's (csrc/Makefile hashes every kernel source into DV_SRC_HASH)
 extern "C" const char* dv_version(void) { return "dvits_hip 0.3 gfx950 src=" DV_SRC_HASH; }
+extern "C" int64_t dv_poisoned_bytes(void) { return poisoned_total().load(); }
+extern "C" int64_t dv_unwritten_bytes(void) { return unwritten_total().load(); }
 // Schedule generations are PROCESS-global and monotonic: a captured sampler graph is keyed on (handle address,
 // generation), and a destroyed handle's address can be handed out again by `new` - with a per-handle counter the new
 // handle's first prepare would reproduce the old key and replay a graph that points into freed memory.
@@ -2207,6 +2209,7 @@ extern "C" int dv_unet_prepare(dv_unet* u, int32_t B, int32_t T, int32_t L, int3
   }
   HIPCHK(hipMalloc((void**)&u->slab, need + 256));
   u->slab_bytes = need;
+  HIPCHK(poison_fill(u->slab, need + 256, nullptr));   // (DVITS_POISON; the packing stream: ahead of every plan-time launch)
   // pass 2: emit the schedule and pack the weights
   {
     Builder b{};
@@ -2313,6 +2316,7 @@ extern "C" int dv_penc_prepare(dv_penc* p, int32_t B, int32_t L, int32_t precisi
   }
   HIPCHK(hipMalloc((void**)&u->slab, need + 256));
   u->slab_bytes = need;
+  HIPCHK(poison_fill(u->slab, need + 256, nullptr));   // (DVITS_POISON; the packing stream: ahead of every plan-time launch)
   {
     Builder b{};
     b.u = u; b.dry = false; b.B = B; b.T = L; b.L = L; b.prec = precision;
@@ -2742,6 +2746,7 @@ struct OpScratch {
     if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
     ptrs.push_back(p);
     if (zero) (void)hipMemsetAsync(p, 0, bytes ? bytes : 16, st);
+    else if (poison_fill(p, bytes ? bytes : 16, st) != hipSuccess) return nullptr;   // (DVITS_POISON)
     return reinterpret_cast<T*>(p);
   }
 };

@@ -5,6 +5,7 @@
 #include "../../include/dvits_hip.h"
 #include "dv_common.h"
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -77,6 +78,32 @@ struct WeightStore {
 };
 
 // ----------------------------------------------------------------------------- plan-time device memory
+// DVITS_POISON (development; read at every fill, so at every prepare: tests flip it inside one process): memory that a plan
+// allocates WITHOUT defining its contents - the denoiser's and the prompt encoder's slab, every dmalloc(zero = false), every
+// OpScratch::get(zero = false) - is filled once, on the plan's stream, before the first operation that could write it:
+//   nan   byte 0xFF: every fp32 word and every bf16 half is a NaN
+//   big   byte 0x4B: ~1.3e7 as fp32 and as bf16 - finite, so a multiply by a zero mask hides it where it would expose a NaN
+// Unset, "0" or anything else: no fill, nothing counted.  Only floating-point payload lives in such memory (indices, counts,
+// flags, tickets and the zero page are allocated zeroed: profiles/poison_audit.txt).  dv_poisoned_bytes() is the running total.
+inline std::atomic<int64_t>& poisoned_total() { static std::atomic<int64_t> n{0}; return n; }
+// ... and dv_unwritten_bytes() the running total of what was REQUESTED that way, counted whether the knob is set or not: the figure a
+// test holds the fill against (a plan's own unzeroed bytes = the growth over its prepare)
+inline std::atomic<int64_t>& unwritten_total() { static std::atomic<int64_t> n{0}; return n; }
+inline int poison_byte() {
+  const char* e = getenv("DVITS_POISON");
+  if (!e) return -1;
+  return strcmp(e, "nan") == 0 ? 0xFF : (strcmp(e, "big") == 0 ? 0x4B : -1);
+}
+inline hipError_t poison_fill(void* p, size_t bytes, hipStream_t st) {
+  if (!p || !bytes) return hipSuccess;
+  unwritten_total() += (int64_t)bytes;
+  const int b = poison_byte();
+  if (b < 0) return hipSuccess;
+  const hipError_t e = hipMemsetAsync(p, b, bytes, st);
+  if (e == hipSuccess) poisoned_total() += (int64_t)bytes;
+  return e;
+}
+
 // `elems` elements of X (never fewer than 16 bytes), owned by `owner`, optionally zeroed on `st`
 template <typename X> X* dmalloc(size_t elems, std::vector<void*>& owner, bool zero, hipStream_t st, PlanError& err) {
   void* p = nullptr;
@@ -84,6 +111,7 @@ template <typename X> X* dmalloc(size_t elems, std::vector<void*>& owner, bool z
   if (hipMalloc(&p, bytes) != hipSuccess) { err.set(DV_ERR_HIP, "hipMalloc failed"); return nullptr; }
   owner.push_back(p);
   if (zero) (void)hipMemsetAsync(p, 0, bytes, st);
+  else if (poison_fill(p, bytes, st) != hipSuccess) { err.set(DV_ERR_HIP, "DVITS_POISON fill failed"); return nullptr; }
   return reinterpret_cast<X*>(p);
 }
 inline void free_owned(std::vector<void*>& owner) {

@@ -798,6 +798,13 @@ extern "C" int dv_plan_set_guidance(dv_plan* p, double scale, int32_t on) {
 
 // rows: utterances in x (the rows of the thresholding; 0 for a plan without it); B: rows of the network's batch (2 x rows of x
 // under guidance); cond_numel: floats of the channel-concat condition that goes with x (guidance stages it twice)
+// (DVITS_POISON: the plan's float buffers - pair buffers, xp, the history slots - are allocated without defined contents; the
+// thresholding workspace holds integer histogram words that every launch zeroes first and is left alone)
+static int plan_poison(float* b, size_t bytes) {
+  HIPCHK(poison_fill(b, bytes, nullptr));
+  if (poison_byte() >= 0) HIPCHK(hipStreamSynchronize(nullptr));   // (the run's stream may not wait for the null stream)
+  return DV_OK;
+}
 static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows, int64_t cond_numel = 0) {
   if (p->cfg_on && (p->cfg_numel != numel || p->cfg_cond_numel != cond_numel)) {
     plan_drop_graph(p);
@@ -807,6 +814,9 @@ static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows, int64_t cond
     HIPCHK(hipMalloc((void**)&p->cfg_in, 2 * numel * sizeof(float)));
     HIPCHK(hipMalloc((void**)&p->cfg_out, 2 * numel * sizeof(float)));
     if (cond_numel > 0) HIPCHK(hipMalloc((void**)&p->cfg_cond, 2 * cond_numel * sizeof(float)));
+    if (int rc = plan_poison(p->cfg_in, 2 * numel * sizeof(float))) return rc;
+    if (int rc = plan_poison(p->cfg_out, 2 * numel * sizeof(float))) return rc;
+    if (cond_numel > 0) if (int rc = plan_poison(p->cfg_cond, 2 * cond_numel * sizeof(float))) return rc;
     p->cfg_numel = numel; p->cfg_cond_numel = cond_numel;
   }
   if (p->thr_ratio >= 0.0 && p->thr_rows != rows) {
@@ -834,10 +844,12 @@ static int plan_buffers(dv_plan* p, int64_t numel, int B, int rows, int64_t cond
     for (float* b : p->m) (void)hipFree(b);
     p->m.clear(); p->xp = nullptr;
     HIPCHK(hipMalloc((void**)&p->xp, numel * sizeof(float)));
+    if (int rc = plan_poison(p->xp, numel * sizeof(float))) return rc;
     for (int s = 0; s < p->n_slots; ++s) {
       float* b = nullptr;
       HIPCHK(hipMalloc((void**)&b, numel * sizeof(float)));
       p->m.push_back(b);
+      if (int rc = plan_poison(b, numel * sizeof(float))) return rc;
     }
     p->buf_numel = numel;
   }

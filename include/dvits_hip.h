@@ -120,6 +120,15 @@ typedef struct dv_mel dv_mel;
 const char* dv_last_error(void);
 /* Library/version probe: returns e.g. "dvits_hip 0.1 gfx950". */
 const char* dv_version(void);
+/* Development: bytes of plan memory filled so far in this process because DVITS_POISON was "nan" (byte 0xFF) or "big" (byte 0x4B)
+ * at a prepare or a single-operator call (development knobs).  The fill covers memory whose contents the plan leaves
+ * undefined: the denoiser's and the prompt encoder's activation slab, and every buffer the row engines and the dv_op_* entry points
+ * allocate without zeroing.  A running total that never goes back; it stays where it is while the variable is unset. */
+int64_t dv_poisoned_bytes(void);
+/* Development: bytes of plan memory REQUESTED so far without defined contents - the same allocations, counted at the same place,
+ * whether DVITS_POISON is set or not.  Its growth over one prepare (or one dv_op_* call, or the first dv_sampler_run of a plan) is
+ * that plan's unzeroed byte count: under `nan` / `big`, dv_poisoned_bytes() must grow by exactly as much. */
+int64_t dv_unwritten_bytes(void);
 
 /* ---- denoiser: UNet1DConditionModel ------------------------------------------------ */
 
