@@ -144,6 +144,7 @@ SIGNATURES = {
     "dv_op_gemm_variant": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_int32)] * 3),
     "dv_op_group_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),
     "dv_op_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
+    "dv_op_attention_prec": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p]),
     "dv_op_attention_frag": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_conv3": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 7 + [C.c_void_p]),
     "dv_op_layer_norm": (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),

@@ -2966,17 +2966,24 @@ extern "C" int dv_op_group_stats(const float* x, float* mean, float* rstd, int32
   return DV_OK;
 }
 
-extern "C" int dv_op_attention(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
-                               int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream) {
+extern "C" int dv_op_attention_prec(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
+                                    int32_t H, int32_t Tq, int32_t Tk, int32_t d, int32_t precision, void* stream) {
   if (!q || !k || !v || !o) return dv_fail(DV_ERR_INVALID, "dv_op_attention: null argument");
+  if (precision != DV_PREC_BF16X3 && precision != DV_PREC_BF16) return dv_fail(DV_ERR_INVALID, "dv_op_attention: precision %d is not a DV_PREC_*", precision);
+  if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return dv_fail(DV_ERR_INVALID, "dv_op_attention: B, H, Tq and Tk must be positive");
   AttnParams a{};
   a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = o; a.o_hi = nullptr; a.o_lo = nullptr;
   a.ldq = a.ldk = a.ldv = a.ldo = H * d;
-  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.d = d; a.scale = 1.0f / sqrtf((float)d); a.nsplit = 3;
+  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.d = d; a.scale = 1.0f / sqrtf((float)d); a.nsplit = precision == DV_PREC_BF16X3 ? 3 : 1;
   HIPCHK(attn_init());
   hipError_t e = launch_attention(a, (hipStream_t)stream);
   if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "attention launch failed: %s (d must be a multiple of 4, <= 64)", hipGetErrorString(e));
   return DV_OK;
+}
+
+extern "C" int dv_op_attention(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
+                               int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream) {
+  return dv_op_attention_prec(q, k, v, bias, o, B, H, Tq, Tk, d, DV_PREC_BF16X3, stream);
 }
 
 // k_attention_frag as the forward runs its cross attention: K | V -> split fragments in the hoisted layout (launch_kv_frag), the

@@ -605,6 +605,11 @@ int dv_op_group_stats(const float* x, float* mean, float* rstd, int32_t B, int32
  * axis as the reference's .view(B,-1,H,d)); bias [B, Tk] additive or NULL. */
 int dv_op_attention(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
                     int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream);
+/* dv_op_attention with the precision mode as an argument: DV_PREC_BF16X3 is dv_op_attention itself (split-bf16 operands, P as one
+ * fp16 plane); DV_PREC_BF16 launches k_attention<., ., 1> as the bf16 fast mode of the forward does - q (pre-scaled), k, v and P each
+ * ONE bf16 plane, fp32 accumulation.  Any other precision: DV_ERR_INVALID. */
+int dv_op_attention_prec(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
+                         int32_t H, int32_t Tq, int32_t Tk, int32_t d, int32_t precision, void* stream);
 /* The same operation on the kernel the forward runs (k_attention_frag): k | v become split-bf16 MFMA fragments of 32-key tiles
  * in the layout of the hoisted cross-attention keys / values, bias [B, Tk] (or NULL) becomes log2-domain rows of whole tiles,
  * and the launcher picks its instantiation (waves per workgroup, key split) from the shape as it does in the forward.  d must

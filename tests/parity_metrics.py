@@ -149,12 +149,58 @@ def expected_probes(model):
     return names
 
 
-def oracle_probes(kw, sd, sample, t, enc, mask_t):
-    """Named intermediates of the oracle, keyed like the engine's probes (channels-last), in schedule order."""
-    import torch.nn.functional as F
+def one_plane(v):
+    """The operand-rounding hook of the bf16 fast mode: v as ONE bf16 plane, in v's own dtype."""
+    return v.to(torch.float32).to(torch.bfloat16).to(v.dtype)
+
+
+class _RoundedOps:
+    """`base` (torch.nn.functional, or torch) with every contraction operand passed through `hook` first: linear, conv1d, matmul,
+    and scaled_dot_product_attention restated as its two products - q d^-1/2 and k rounded, the mask added to the logits, exp(s - max)
+    and v rounded, the denominator from the unrounded exponentials.  Everything else is `base`'s own: torch.einsum among it, so the
+    two small products of the pooled text embedding (oracle/unet_ref.py text_time_embedding) keep their operands unrounded."""
+
+    def __init__(self, base, hook):
+        self._base, self._hook = base, hook
+
+    def __getattr__(self, name):
+        return getattr(self._base, name)
+
+    def linear(self, x, w, b=None):
+        return self._base.linear(self._hook(x), self._hook(w), b)
+
+    def conv1d(self, x, w, b=None, **kwargs):
+        return self._base.conv1d(self._hook(x), self._hook(w), b, **kwargs)
+
+    def matmul(self, a, b):
+        return self._base.matmul(self._hook(a), self._hook(b))
+
+    def scaled_dot_product_attention(self, q, k, v, attn_mask=None, dropout_p=0.0, is_causal=False):
+        assert dropout_p == 0.0 and not is_causal
+        s = self._hook(q * q.shape[-1] ** -0.5) @ self._hook(k).transpose(-1, -2)
+        if attn_mask is not None:
+            s = s + attn_mask
+        pr = torch.exp(s - s.amax(-1, keepdim=True))
+        return (self._hook(pr) @ self._hook(v)) / pr.sum(-1, keepdim=True)
+
+
+def _hooked(R, hook):
+    """Module attributes of the oracle module R to swap while `hook` is on: {name: replacement}."""
+    return {} if hook is None else {n: _RoundedOps(getattr(R, n), hook) for n in ("F", "torch") if hasattr(R, n)}
+
+
+def oracle_probes(kw, sd, sample, t, enc, mask_t, round_operand=None):
+    """Named intermediates of the oracle, keyed like the engine's probes (channels-last), in schedule order.  round_operand: a hook
+    applied to both operands of every F.linear / F.conv1d / attention product of the forward, the einsum pair of the pooled text
+    embedding excepted (one_plane: a whole-forward emulation
+    of the bf16 fast mode); None (the default) leaves the oracle as it is."""
     from conftest import oracle_cfg
     from oracle import unet_ref as R
     out = {}
+    swapped = {n: getattr(R, n) for n in _hooked(R, round_operand)}
+    for n, v in _hooked(R, round_operand).items():
+        setattr(R, n, v)
+    F = R.F
     orig = {n: getattr(R, n) for n in ("resnet_block", "transformer_1d", "downsample", "upsample", "transformer_block",
                                        "attention")}
 
@@ -206,7 +252,7 @@ def oracle_probes(kw, sd, sample, t, enc, mask_t):
         pr = {}
         y = R.unet_forward(sd, oracle_cfg(kw), sample, t, enc, mask_t, probes=pr)
     finally:
-        for n, f in orig.items():
+        for n, f in list(orig.items()) + list(swapped.items()):
             setattr(R, n, f)
     out["emb"] = pr["emb"][:, None, :]
     tap("conv_in", pr["conv_in"])
@@ -221,16 +267,20 @@ def prompt_probe_names(n_layers):
     return names + ["out_proj"]
 
 
-def prompt_oracle_probes(sd, prompt, lengths, n_layers, num_heads=8):
+def prompt_oracle_probes(sd, prompt, lengths, n_layers, num_heads=8, round_operand=None):
     """oracle.prompt_ref.prompt_encoder with its named intermediates, keyed like the engine's probes: (y [B, L, C_out], dict of
     [B, L, C]).  `pre` and `layerN` are the oracle's own probes; `layerN.attn` (after self-attention + residual + mask),
     `layerN.ffn1` (relu(k^-1/2 x the nine taps' sum), 4H wide, padding frames NOT masked) and `out_proj` (the masked out_proj
     ConvLayer, before the last LayerNorm) are taken by wrapping enc_sa_layer / ffn / conv_layer, which the oracle calls through
     its module globals; the wrappers call the original functions for what they return, so the oracle computes what it always
-    computes."""
-    import torch.nn.functional as F
+    computes.  round_operand: oracle_probes' hook, here on every F.linear and torch.matmul (the k = 1 ConvTBC and both attention
+    products: q d^-1/2, k, the normalised probabilities and v are each rounded)."""
     from oracle import prompt_ref as R
     out = {}
+    swapped = {n: getattr(R, n) for n in _hooked(R, round_operand)}
+    for n, v in _hooked(R, round_operand).items():
+        setattr(R, n, v)
+    F = R.F
     orig = {n: getattr(R, n) for n in ("enc_sa_layer", "ffn", "conv_layer")}
     keep = R.sequence_mask(lengths, prompt.shape[2]).to(prompt.dtype)[:, :, None]      # [B, L, 1]
 
@@ -267,7 +317,7 @@ def prompt_oracle_probes(sd, prompt, lengths, n_layers, num_heads=8):
         pr = {}
         y = R.prompt_encoder(sd, prompt, lengths, n_layers, num_heads, probes=pr)
     finally:
-        for n, f in orig.items():
+        for n, f in list(orig.items()) + list(swapped.items()):
             setattr(R, n, f)
     out.update(pr)
     names = prompt_probe_names(n_layers)
@@ -320,7 +370,17 @@ def seam_figures(per_frame, rows):
 # ONE fp16 plane before P V (tests/test_gpu_ops.py test_attention_frag).  The emulation is what sets the per-frame bound of the
 # GPU test (isolated_bound): it carries the cancellation of  x W' - mean u  at a large row mean that a fixed bound would have to
 # guess.  `fault` plants what a kernel could get wrong only in this regime (FAULTS).
+#
+# emulate="bf16" is the fast mode (precision="bf16": the plain schedule, DESIGN.md "Precision"): every contraction operand ONE bf16
+# plane - the raw LayerNorm row, the gamma-folded weight W gamma (folded first, then rounded, as the packer does), the GroupNorm
+# affine's result, q, k, v; q is multiplied by fp32(d^-1/2 log2 e) BEFORE it is rounded (attn_tile.h keeps the scores in the log2
+# domain and scales the query, not the logit), the logits and the mask are added in fp32, and exp2(s - max) is rounded to ONE bf16
+# plane before P V while the denominator sums the unrounded values.  Two faults belong to this mode: "mask_tail" - the mask bias
+# left off the keys of the last 32-key sub-tile; "p_fp16" - P rounded to fp16 where bf16 is documented.
 FAULTS = ("lost_lo", "mean_from_bf16", "beta_sign", "tscale", "skip_stats")
+BF16_FAULTS = ("mean_from_bf16", "beta_sign", "tscale", "skip_stats", "mask_tail", "p_fp16")
+BF16_FLOOR = 2.0 ** -9      # half an ulp of an 8-bit significand: what one bf16 plane can hold of an operand at all
+LOG2E = 1.44269504088896340736
 
 
 def _planes(v, lo=True):
@@ -332,9 +392,14 @@ def _planes(v, lo=True):
     return hi.double() + (v32 - hi).to(torch.bfloat16).double()
 
 
+def _operand(v, emulate):
+    """What a contraction holds of the operand v: v itself, its two bf16 planes (emulate=True), its hi plane alone ("bf16")."""
+    return _planes(v, lo=emulate != "bf16") if emulate else v
+
+
 def _linear(x, W, b, emulate):
     import torch.nn.functional as F
-    return F.linear(_planes(x), _planes(W), b) if emulate else F.linear(x, W, b)
+    return F.linear(_operand(x, emulate), _operand(W, emulate), b)
 
 
 def ln_linear(x, gamma, beta, W, b, emulate=False, fault=None, eps=1e-5, stats=None, acc32=False):
@@ -355,9 +420,10 @@ def ln_linear(x, gamma, beta, W, b, emulate=False, fault=None, eps=1e-5, stats=N
         mean, rstd = (torch.as_tensor(s).double().reshape(-1, 1) for s in stats)
     if fault == "mean_from_bf16":
         mean = _planes(x, lo=False).mean(-1, keepdim=True)
-    Wf = _planes(W * gamma[None, :])
+    Wf = _planes(W * gamma[None, :], lo=emulate != "bf16")
     bf = (-1.0 if fault == "beta_sign" else 1.0) * (W @ beta) + (0.0 if b is None else b)
-    xp = _planes(x, lo=fault != "lost_lo")
+    xp = _planes(x, lo=fault != "lost_lo" and emulate != "bf16")
+    assert not (acc32 and emulate == "bf16")
     if acc32:    # the three products of the split-bf16 contraction (hi hi + hi lo + lo hi; lo lo is never formed), float32 accumulation
         u32, b32 = (W * gamma[None, :]).sum(-1).float(), bf.float()
         xh, wh = _planes(x, lo=False).float(), _planes(W * gamma[None, :], lo=False).float()
@@ -367,11 +433,25 @@ def ln_linear(x, gamma, beta, W, b, emulate=False, fault=None, eps=1e-5, stats=N
     return rstd * (xp @ Wf.t() - mean * Wf.sum(-1)) + bf
 
 
-def _sdpa(q, k, v, heads, bias, emulate):
+def _sdpa(q, k, v, heads, bias, emulate, fault=None):
     import math
     B, Tq, C = q.shape
     d = C // heads
     q, k, v = (a.reshape(B, -1, heads, d).transpose(1, 2) for a in (q, k, v))
+    if fault == "mask_tail" and bias is not None:
+        Tk = k.shape[-2]
+        bias = bias.clone()
+        bias[..., (Tk - 1) // 32 * 32:] = 0.0
+    if emulate == "bf16":
+        qs = torch.tensor(1.0 / math.sqrt(d), dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32)
+        s = (_planes(q.float() * qs, lo=False) @ _planes(k, lo=False).transpose(-1, -2)).float()
+        if bias is not None:
+            s = s + (bias.float() * torch.tensor(LOG2E, dtype=torch.float32))[:, None]
+        s = s.double()
+        pr = torch.exp2(s - s.amax(-1, keepdim=True))
+        p1 = pr.half().double() if fault == "p_fp16" else pr.float().to(torch.bfloat16).double()
+        o = (p1 @ _planes(v, lo=False)) / pr.sum(-1, keepdim=True)
+        return o.transpose(1, 2).reshape(B, Tq, C)
     s = q @ k.transpose(-1, -2) / math.sqrt(d)
     if emulate:
         s = s.float() if bias is None else s.float() + bias.float()[:, None]
@@ -381,6 +461,13 @@ def _sdpa(q, k, v, heads, bias, emulate):
     pr = torch.exp(s - s.amax(-1, keepdim=True))
     o = ((pr.half().double() if emulate else pr) @ v) / pr.sum(-1, keepdim=True)
     return o.transpose(1, 2).reshape(B, Tq, C)
+
+
+def sdpa_fp64(q, k, v, heads, bias=None, emulate=False, fault=None):
+    """softmax(q k^T d^-1/2 + bias) v on [B, T, heads d] tensors, bias additive [B, Tk] or None, in fp64 - or as the documented
+    arithmetic does it (emulate / fault: above)."""
+    q, k, v = (torch.as_tensor(a).double() for a in (q, k, v))
+    return _sdpa(q, k, v, heads, None if bias is None else torch.as_tensor(bias).double()[:, None, :], emulate, fault)
 
 
 def attn_chain_fp64(sd, tb, which, x, heads, enc=None, mask=None, emulate=False, fault=None):
@@ -398,7 +485,7 @@ def attn_chain_fp64(sd, tb, which, x, heads, enc=None, mask=None, emulate=False,
         e = torch.as_tensor(enc).double()
         k, v = _linear(e, W(a + "to_k.weight"), None, emulate), _linear(e, W(a + "to_v.weight"), None, emulate)
         bias = None if mask is None else ((1.0 - torch.as_tensor(mask).double()) * -10000.0)[:, None, :]
-    o = _sdpa(q, k, v, heads, bias, emulate)
+    o = _sdpa(q, k, v, heads, bias, emulate, fault)
     return _linear(o, W(a + "to_out.0.weight"), W(a + "to_out.0.bias"), emulate) + x
 
 
@@ -415,11 +502,10 @@ def _group_affine(x, groups, gamma, beta, eps, stats_from=None):
     return a[:, None, :], (beta[None, :] - mean[:, grp] * a)[:, None, :]
 
 
-def _conv(h, W, b, emulate):
+def _conv(h, W, b, emulate, stride=1):
     import torch.nn.functional as F
-    if emulate:
-        h, W = _planes(h), _planes(W)
-    return F.conv1d(h.permute(0, 2, 1), W, b, padding=W.shape[-1] // 2).permute(0, 2, 1)
+    return F.conv1d(_operand(h, emulate).permute(0, 2, 1), _operand(W, emulate), b, stride=stride,
+                    padding=W.shape[-1] // 2).permute(0, 2, 1)
 
 
 def proj_in_fp64(sd, p, x, groups, emulate=False):
@@ -459,11 +545,43 @@ def resnet_fp64(sd, p, x, emb, groups, skip=None, eps=1e-5, emulate=False, fault
     return x + h
 
 
-def isolated_bound(emulated, want):
+def isolated_bound(emulated, want, mode=None):
     """Bound for one launch (or one stretch between taps) in isolation, whole tensor and every frame: FF_TAIL_BOUND, or - where the
     inputs make the documented arithmetic itself cost more - 2 x the worst frame of its host emulation + 2^-16 (the factor 2 and
-    the 2^-16 as tests/test_gpu_ops.py test_attention_frag argues them)."""
+    the 2^-16 as tests/test_gpu_ops.py test_attention_frag argues them).  mode="bf16": the same form for the one-plane fast mode,
+    2 x the worst frame of the emulate="bf16" restatement + 2^-9 (BF16_FLOOR: with a single valid key the emulation is exact);
+    FF_TAIL_BOUND is a parity-mode figure and does not enter."""
+    if mode == "bf16":
+        return 2.0 * frame_errors(emulated, want)["worst"] + BF16_FLOOR
+    assert mode is None, mode
     return max(FF_TAIL_BOUND, 2.0 * frame_errors(emulated, want)["worst"] + 2.0 ** -16)
+
+
+def conv_in_fp64(sd, sample, emulate=False):
+    """conv_in: sample [B, T, Cin] channels-last -> the tapped conv_in."""
+    W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
+    return _conv(torch.as_tensor(sample).double(), W("conv_in.weight"), W("conv_in.bias"), emulate)
+
+
+def resample_fp64(sd, p, x, size=None, emulate=False):
+    """Downsample2D (p = "....downsamplers.0.": Conv1d k 3, stride 2, padding 1) or Upsample2D (p = "....upsamplers.0.": nearest to
+    `size` frames - twice the input's when None - then Conv1d k 3, padding 1), x channels-last = the tapped input."""
+    import torch.nn.functional as F
+    W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
+    x = torch.as_tensor(x).double()
+    if "downsamplers" in p:
+        return _conv(x, W(p + "conv.weight"), W(p + "conv.bias"), emulate, stride=2)
+    x = F.interpolate(x.permute(0, 2, 1), size=2 * x.shape[1] if size is None else size, mode="nearest").permute(0, 2, 1)
+    return _conv(x, W(p + "conv.weight"), W(p + "conv.bias"), emulate)
+
+
+def conv_out_fp64(sd, x, groups, eps=1e-5, emulate=False):
+    """conv_norm_out -> SiLU -> conv_out: x = the tapped last transformer (up_blocks.3.attentions.2), result = the output y, channels-last."""
+    import torch.nn.functional as F
+    W = lambda n: sd[n].detach().cpu().to(torch.float64)    # noqa: E731
+    x = torch.as_tensor(x).double()
+    a, b = _group_affine(x, groups, W("conv_norm_out.weight"), W("conv_norm_out.bias"), eps)
+    return _conv(F.silu(a * x + b), W("conv_out.weight"), W("conv_out.bias"), emulate)
 
 
 def resnet_input_taps(n_levels=4, layers=2):

@@ -2,7 +2,8 @@
 (oracle/) and the golden vectors captured from the reference (tests/golden/).
 
 Bar (BASELINE.json north_star): UNet output <= 1e-3 relative to the fp32 reference; the parity
-mode (bf16x3) is asserted at 2e-4, the fast bf16 mode at 3e-2 (reported, not graded)."""
+mode (bf16x3) is asserted at 2e-4, the fast bf16 mode at 3e-2 here as one whole-tensor figure; its per-stretch,
+per-frame parity against a one-plane emulation is in tests/test_gpu_bf16_mode.py."""
 import os
 
 import numpy as np
