@@ -12,7 +12,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define DV_ATTN_KVSPLIT_MAX 16
 #endif
 
-__device__ __forceinline__ unsigned apk(float lo, float hi) { return dv_cvt_pk_bf16(lo, hi); }
+__device__ __forceinline__ unsigned apk(float lo, float hi) { return pk(lo, hi); }
 __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 

@@ -139,6 +139,10 @@ __device__ __forceinline__ unsigned dv_cvt_pk_bf16(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, dv_bf16x2));
 }
 
+__device__ __forceinline__ unsigned pk(float lo, float hi) { return dv_cvt_pk_bf16(lo, hi); }
+// 16-byte slot swizzle of the resident LDS operands (128-byte rows of 64 bf16 channels): slot s of `row` lives at s ^ swz(row)
+__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
+
 // P V of the attention kernels (parity mode).  DV_ATTN_PF16 = 1 (default since round 4): the probabilities enter as ONE fp16
 // plane (11 significant bits, round to nearest even: v_cvt_pk_f16_f32) and V as split fp16 (hi + lo): two products
 // P Vhi + P Vlo on v_mfma_f32_32x32x16_f16.  [Rounds 1-3: P and V both split bf16, three products; the softmax loop is bound
@@ -279,6 +283,13 @@ __device__ __forceinline__ void store_planes8(unsigned short* hi, unsigned short
     pair_swap32(l[1], l[3]);
     dv_st16(lo + o + 8 * lh, make_uint4(l[0], l[1], l[2], l[3]));
   }
+}
+
+// The fp32 row of the same layouts (R = 16 / 8 values): `o` = element offset of THIS LANE's first column (the 4 lh included)
+template <int R>
+__device__ __forceinline__ void store_row(float* out, size_t o, const float (&v)[R]) {
+#pragma unroll
+  for (int g = 0; g < R / 4; ++g) dv_st16(out + o + 8 * g, make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]));
 }
 
 // GELU with the exact-erf definition (reference unet1d/activations / F.gelu default), erf by Abramowitz-Stegun 7.1.26

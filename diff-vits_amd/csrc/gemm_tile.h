@@ -607,73 +607,24 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 #pragma unroll
       for (int r = 0; r < 8; ++r) vv[r] = m_ok ? vv[r] : 0.f;
       DV_TRACE(16);
-#if DV_GNX_STATS_FIRST
-      // (round 5: the block statistics are published BEFORE this wave's result stores are issued - the other workgroups of the
-      // launch wait for the words, nobody waits for the stores; k_chain_ff has had this order since round 4)
-      if (p.stats16) {                               // this wave's 32 x 16 block: (sum, squared deviations about its own mean)
-        float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) a1 += vv[r];
-        a1 = wave_sum64(a1);
-        const float mb = padded ? a1 / (float)(16 * blk_cnt(mrow0)) : a1 * (1.0f / 512.0f);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { const float dv = (!padded || m_ok) ? vv[r] - mb : 0.f; a2 = fmaf(dv, dv, a2); }
-        a2 = wave_sum64(a2);
-        if (lane == 0 && mrow0 < p.M) {
-          const size_t e = (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol >> 4);
-          reinterpret_cast<float2*>(p.stats16)[e] = make_float2(a1, a2);
-          if (gnx_h)
-            __hip_atomic_store(p.gnx.xchg + e, (unsigned long long)__float_as_uint(a1) | ((unsigned long long)__float_as_uint(a2) << 32),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-#endif
+      // this wave's 32 x 16 block statistics (gnx_device.h).  DV_GNX_STATS_FIRST: published BEFORE the result stores are issued - the
+      // other workgroups of the launch wait for the words, nobody waits for the stores; k_chain_ff has had this order since round 4
+      const bool st_in = !padded || m_ok, st_pub = lane == 0 && mrow0 < p.M;   // (a zeroed row beyond M of an unpadded row space counts)
+      const size_t st_e = (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol >> 4);
+      if (DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e);
       if (m_in) {                                    // (padding rows are stored as zeros)
         const size_t ob = (size_t)m * p.ldo + ncol;
-        if (p.out) {
-#pragma unroll
-          for (int g = 0; g < 2; ++g)
-            dv_st16(p.out + ob + 4 * lh + 8 * g, make_float4(vv[4 * g], vv[4 * g + 1], vv[4 * g + 2], vv[4 * g + 3]));
-        }
+        if (p.out) store_row(p.out, ob + 4 * lh, vv);
         if (p.out_hi) store_planes8(p.out_hi, p.out_lo, ob, lh, vv);
       }
       DV_TRACE(17);
-#if !DV_GNX_STATS_FIRST
-      if (p.stats16) {                               // this wave's 32 x 16 block: (sum, squared deviations about its own mean)
-        float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) a1 += vv[r];
-        a1 = wave_sum64(a1);
-        const float mb = padded ? a1 / (float)(16 * blk_cnt(mrow0)) : a1 * (1.0f / 512.0f);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { const float dv = (!padded || m_ok) ? vv[r] - mb : 0.f; a2 = fmaf(dv, dv, a2); }
-        a2 = wave_sum64(a2);
-        if (lane == 0 && mrow0 < p.M) {
-          const size_t e = (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol >> 4);
-          reinterpret_cast<float2*>(p.stats16)[e] = make_float2(a1, a2);
-          if (gnx_h)
-            __hip_atomic_store(p.gnx.xchg + e, (unsigned long long)__float_as_uint(a1) | ((unsigned long long)__float_as_uint(a2) << 32),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-#endif
+      if (!DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e);
       DV_TRACE(18);
       if (gnx_h) {
         gnx_table(NWV);
         if (m_in) {
           float y[8];
-#pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            const int cl = wn * 32 + coff + 4 * lh + 8 * g;
-            const float4 sa = *reinterpret_cast<const float4*>(s_gA + cl);
-            const float4 sb = *reinterpret_cast<const float4*>(s_gB + cl);
-            y[4 * g] = fmaf(vv[4 * g], sa.x, sb.x); y[4 * g + 1] = fmaf(vv[4 * g + 1], sa.y, sb.y);
-            y[4 * g + 2] = fmaf(vv[4 * g + 2], sa.z, sb.z); y[4 * g + 3] = fmaf(vv[4 * g + 3], sa.w, sb.w);
-          }
-          if (p.gnx.silu) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) y[r] = y[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[r]));
-          }
+          gnx_normalise(vv, s_gA, s_gB, wn * 32 + coff + 4 * lh, p.gnx.silu, y);
           store_planes8(p.gnx.y_hi, p.gnx.y_lo, (size_t)m * p.N + ncol, lh, y);
         }
       }
@@ -933,36 +884,13 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = vv[r];
       }
-#if DV_GNX_STATS_FIRST
-      // (the 32x16 block statistics - published to the other workgroups of the launch when a GroupNorm is finished here - go out
-      // BEFORE this fragment's result stores are issued: the words are what the launch waits for)
-      if (p.stats16) {
-        // per (32-row, 16-column) block: (sum, squared deviations from the block's OWN mean) - no E[x^2] - mean^2
-        // cancellation when |mean| >> spread; the consumer combines blocks with the parallel-variance formula in fp64.
-        // Registers 0-7 / 8-15 are the fragment's first / second 16 columns (column = 8g + 4lh + e, r = 4g + e);
-        // every lane holds columns of both halves, so both sums run over all 64 lanes.
-        float a1[2] = {0.f, 0.f}, a2[2] = {0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a1[r >> 3] += vv[r];
-        auto wsum = [&](float v) { return wave_sum64(v); };   // (DPP + scalar registers: dv_device.h)
-        a1[0] = wsum(a1[0]); a1[1] = wsum(a1[1]);
-        const float inv_n = padded ? 1.0f / (float)(16 * blk_cnt(mrow0)) : 1.0f / 512.0f;
-        const float mb[2] = {a1[0] * inv_n, a1[1] * inv_n};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { const float dv = (!padded || m_ok) ? vv[r] - mb[r >> 3] : 0.f; a2[r >> 3] = fmaf(dv, dv, a2[r >> 3]); }
-        a2[0] = wsum(a2[0]); a2[1] = wsum(a2[1]);
-        const int cb0 = (n0 + (wn * FN + j) * 32) >> 4;
-        if (lane < 2 && mrow0 < p.M && (cb0 + lane) * 16 < p.N) {
-          float2* const dst = reinterpret_cast<float2*>(p.stats16) + (size_t)(mrow0 >> 5) * (p.N >> 4) + cb0 + lane;
-          const float2 val = make_float2(lane ? a1[1] : a1[0], lane ? a2[1] : a2[0]);
-          *dst = val;
-          if (gnx)     // for the other workgroups of this launch: one 8-byte word (sum, M2), written through
-            __hip_atomic_store(p.gnx.xchg + (size_t)(mrow0 >> 5) * (p.N >> 4) + cb0 + lane,
-                               (unsigned long long)__float_as_uint(val.x) | ((unsigned long long)__float_as_uint(val.y) << 32),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-#endif
+      // the fragment's two 32x16 block statistics (gnx_device.h), published for the other workgroups of the launch when a GroupNorm
+      // is finished here.  DV_GNX_STATS_FIRST: BEFORE this fragment's result stores are issued - the words are what the launch waits for
+      const int cb0 = (n0 + (wn * FN + j) * 32) >> 4;  // lanes 0 / 1 publish blocks cb0 / cb0 + 1
+      const bool st_in = !padded || m_ok, st_pub = lane < 2 && mrow0 < p.M && (cb0 + lane) * 16 < p.N;
+      const size_t st_e = (size_t)(mrow0 >> 5) * (p.N >> 4) + cb0 + lane;
+      unsigned long long* const st_x = gnx ? p.gnx.xchg : nullptr;
+      if (DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<16, true>(p.stats16, st_x, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e, lane);
       if (p.epi == EPI_STORE_NCT) {
         // [B, N, T_out]: the 32 lanes of a half-wave write 32 consecutive frames of one channel
         if (m_ok) {
@@ -976,11 +904,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
       } else if (m_in) {                              // (padding rows are stored as zeros)
         if (full) {                                  // planes as 16-byte stores: dv_device.h store_planes16
           const size_t ob = (size_t)m * p.ldo + nf;
-          if (p.out) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-              dv_st16(p.out + ob + 8 * g, make_float4(vv[4 * g], vv[4 * g + 1], vv[4 * g + 2], vv[4 * g + 3]));
-          }
+          if (p.out) store_row(p.out, ob, vv);
           if (p.out_hi) store_planes16(p.out_hi, p.out_lo, ob - 4 * lh, lh, vv);
         } else {
 #pragma unroll
@@ -1037,34 +961,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
           reinterpret_cast<float2*>(p.stats)[(size_t)(mrow0 >> 5) * p.N + n] =
               make_float2(fmaf(cnt, kk, s1[0]), fmaxf(s2[0] - s1[0] * s1[0] / cnt, 0.f));
       }
-#if !DV_GNX_STATS_FIRST
-      if (p.stats16) {
-        // per (32-row, 16-column) block: (sum, squared deviations from the block's OWN mean) - no E[x^2] - mean^2
-        // cancellation when |mean| >> spread; the consumer combines blocks with the parallel-variance formula in fp64.
-        // Registers 0-7 / 8-15 are the fragment's first / second 16 columns (column = 8g + 4lh + e, r = 4g + e);
-        // every lane holds columns of both halves, so both sums run over all 64 lanes.
-        float a1[2] = {0.f, 0.f}, a2[2] = {0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a1[r >> 3] += vv[r];
-        auto wsum = [&](float v) { return wave_sum64(v); };   // (DPP + scalar registers: dv_device.h)
-        a1[0] = wsum(a1[0]); a1[1] = wsum(a1[1]);
-        const float inv_n = padded ? 1.0f / (float)(16 * blk_cnt(mrow0)) : 1.0f / 512.0f;
-        const float mb[2] = {a1[0] * inv_n, a1[1] * inv_n};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { const float dv = (!padded || m_ok) ? vv[r] - mb[r >> 3] : 0.f; a2[r >> 3] = fmaf(dv, dv, a2[r >> 3]); }
-        a2[0] = wsum(a2[0]); a2[1] = wsum(a2[1]);
-        const int cb0 = (n0 + (wn * FN + j) * 32) >> 4;
-        if (lane < 2 && mrow0 < p.M && (cb0 + lane) * 16 < p.N) {
-          float2* const dst = reinterpret_cast<float2*>(p.stats16) + (size_t)(mrow0 >> 5) * (p.N >> 4) + cb0 + lane;
-          const float2 val = make_float2(lane ? a1[1] : a1[0], lane ? a2[1] : a2[0]);
-          *dst = val;
-          if (gnx)     // for the other workgroups of this launch: one 8-byte word (sum, M2), written through
-            __hip_atomic_store(p.gnx.xchg + (size_t)(mrow0 >> 5) * (p.N >> 4) + cb0 + lane,
-                               (unsigned long long)__float_as_uint(val.x) | ((unsigned long long)__float_as_uint(val.y) << 32),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-#endif
+      if (!DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<16, true>(p.stats16, st_x, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e, lane);
     }
     }
   DV_TRACE(18);                                      // statistics of every fragment written
@@ -1082,17 +979,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
         const int nfr = n0 + (wn * FN + j) * 32;
         if (al8 && nfr + 32 <= p.N) {                  // (wave-uniform) the whole fragment: 16-byte plane stores
           float y[16];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const float4 sa = *reinterpret_cast<const float4*>(s_gA + cl + 8 * g);
-            const float4 sb = *reinterpret_cast<const float4*>(s_gB + cl + 8 * g);
-            y[4 * g] = fmaf(acc[i][j][4 * g], sa.x, sb.x); y[4 * g + 1] = fmaf(acc[i][j][4 * g + 1], sa.y, sb.y);
-            y[4 * g + 2] = fmaf(acc[i][j][4 * g + 2], sa.z, sb.z); y[4 * g + 3] = fmaf(acc[i][j][4 * g + 3], sa.w, sb.w);
-          }
-          if (p.gnx.silu) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) y[r] = y[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[r]));
-          }
+          gnx_normalise(acc[i][j], s_gA, s_gB, cl, p.gnx.silu, y);
           store_planes16(p.gnx.y_hi, p.gnx.y_lo, (size_t)m * p.N + nfr, lh, y);
           continue;
         }
@@ -1105,7 +992,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
                         fmaf(acc[i][j][4 * g + 2], sa.z, sb.z), fmaf(acc[i][j][4 * g + 3], sa.w, sb.w)};
           if (p.gnx.silu) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = y[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[e]));
+            for (int e = 0; e < 4; ++e) y[e] = dv_silu(y[e]);
           }
           const size_t o = (size_t)m * p.N + n0 + cl + 8 * g;
           const unsigned h01 = cvt_pk_bf16(y[0], y[1]), h23 = cvt_pk_bf16(y[2], y[3]);

@@ -1,11 +1,18 @@
-// GroupNorm of a producer's OWN output finished inside its launch (GnxParams, dv_common.h): the part every producer kernel
-// shares - gemm_tile.h (the contraction kernel) and kernels_chain.hip (k_chain_ff).  The caller has written its tile's 32x16
-// block statistics (sum, M2 about the block mean) to the exchange words; gnx_finish_table
-//   1. reduces, one wave per group, the statistics of the groups its tile's columns belong to (polling the exchange words of
-//      the other workgroups of the launch - all resident, the planner checked; bounded and flagged, never a hang),
-//   2. leaves the per-column affine (scale, shift) of its tile in shared memory (sh.gA / sh.gB) for the caller's own
-//      normalise-and-store pass, and
-//   3. for a concatenated consumer normalises a slice of the skip tensor's columns for the tile's rows itself.
+// GroupNorm of a producer's OWN output finished inside its launch (GnxParams, dv_common.h): the tail every producer of a
+// GroupNorm input ends its epilogue with - k_gemm's half- and full-fragment epilogues (gemm_tile.h), the conv kernels
+// (kernels_conv.hip), k_chain_ff / k_chain_xa_ff (kernels_chain.hip) and k_ff_split (kernels_ffsplit.hip).  In order:
+//   gnx_block_sums    the 32x16 block statistics (sum, M2 about the block's own mean) of a half (8 values per lane, one block)
+//                     or full (16 values, two blocks) fragment;
+//   gnx_publish       stores them to stats16 and, for the other workgroups of the launch, as one 8-byte exchange word
+//                     (gnx_word); the caller chooses the publishing lane and its guard;
+//   gnx_finish_table  1. reduces, one wave per group, the statistics of the groups its tile's columns belong to (polling the
+//                        exchange words of the other workgroups of the launch - all resident, the planner checked; bounded and
+//                        flagged, never a hang),
+//                     2. leaves the per-column affine (scale, shift) of its tile in shared memory (sh.gA / sh.gB), and
+//                     3. for a concatenated consumer normalises a slice of the skip tensor's columns for the tile's rows itself;
+//   gnx_normalise     y = v * gA + gB of the caller's fragment, then SiLU (dv_silu); the caller zeroes / skips rows that do not
+//                     exist and stores the split planes.
+// All of it runs in epilogues only: nothing here loads before its caller's k-loop ("Compiler-inserted drains").
 #pragma once
 #include "dv_common.h"
 #include "dv_device.h"
@@ -24,6 +31,76 @@ struct GnxShared {
   __attribute__((aligned(16))) float gA[BN < 64 ? 64 : BN], gB[BN < 64 ? 64 : BN];
   __attribute__((aligned(16))) float gA2[DV_GSK], gB2[DV_GSK];
 };
+
+__device__ __forceinline__ float dv_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+
+// The exchange word of one 32x16 block: (sum | M2 << 32).  EMPTY is all ones; a published pair is finite.
+__device__ __forceinline__ unsigned long long gnx_word(float a1, float a2) {
+  return (unsigned long long)__float_as_uint(a1) | ((unsigned long long)__float_as_uint(a2) << 32);
+}
+// Block `e` of [M / 32][N / 16]: to memory for later launches and - xchg set - written through for the workgroups of this one.
+__device__ __forceinline__ void gnx_publish(float* stats16, unsigned long long* xchg, size_t e, float a1, float a2) {
+  reinterpret_cast<float2*>(stats16)[e] = make_float2(a1, a2);
+  if (xchg) __hip_atomic_store(xchg + e, gnx_word(a1, a2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// (sum, squared deviations from the block's OWN mean) of the wave's 32-row block(s), the same in every lane - no
+// E[x^2] - mean^2 cancellation when |mean| >> spread; the consumer combines blocks with the parallel-variance formula in fp64.
+// R = 8: v[4g + e] = column 8g + 4lh + e of one 16-column block.  R = 16: registers 0-7 / 8-15 are the fragment's first /
+// second 16 columns; every lane holds columns of both, so all sums run over all 64 lanes.  `in1` / `in2`: this lane's row
+// enters the sum / the deviations (a caller that has zeroed its padding rows passes in1 = true; in2 = true for a zeroed row
+// beyond M of an UNPADDED row space, which has always contributed (0 - mean)^2); `cnt`: frames of the block that exist.
+// RCP: the mean is a1 * (1 / (16 cnt)), else a1 / (16 cnt).  The two round differently when cnt is no power of two (both are
+// exact for a whole block, 1 / 512), and each site keeps the form it was written with: the other one would change bits of M2
+// in every short last block.
+template <int R, bool RCP>
+__device__ __forceinline__ void gnx_block_sums(const float (&v)[R], const bool in1, const bool in2, const int cnt, float (&a1)[R / 8],
+                                               float (&a2)[R / 8]) {
+  static_assert(R == 8 || R == 16, "half or full fragment");
+  float mb[R / 8];
+#pragma unroll
+  for (int b = 0; b < R / 8; ++b) a1[b] = a2[b] = 0.f;
+#pragma unroll
+  for (int r = 0; r < R; ++r) a1[r >> 3] += in1 ? v[r] : 0.f;
+  const float n = (float)(16 * cnt);
+#pragma unroll
+  for (int b = 0; b < R / 8; ++b) {
+    a1[b] = wave_sum64(a1[b]);                     // (DPP + scalar registers: dv_device.h)
+    mb[b] = RCP ? a1[b] * (1.0f / n) : a1[b] / n;
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) { const float dv = in2 ? v[r] - mb[r >> 3] : 0.f; a2[r >> 3] = fmaf(dv, dv, a2[r >> 3]); }
+#pragma unroll
+  for (int b = 0; b < R / 8; ++b) a2[b] = wave_sum64(a2[b]);
+}
+
+// Both steps: the wave's block sums, then the lanes with `pub` set publish block `e` - of a full fragment its block `blk`
+// (lanes 0 / 1 publish blocks e0 / e0 + 1).  A plain function, called once or twice per fragment: a capturing lambda around
+// these steps cost k_gemm's 128 x 128 tile 40 registers and sent it through scratch memory.
+template <int R, bool RCP>
+__device__ __forceinline__ void gnx_block_stats(float* stats16, unsigned long long* xchg, const float (&v)[R], const bool in1, const bool in2,
+                                                const int cnt, const bool pub, const size_t e, const int blk = 0) {
+  float a1[R / 8], a2[R / 8];
+  gnx_block_sums<R, RCP>(v, in1, in2, cnt, a1, a2);
+  if (pub) gnx_publish(stats16, xchg, e, blk ? a1[R / 8 - 1] : a1[0], blk ? a2[R / 8 - 1] : a2[0]);
+}
+
+// The caller's fragment through the table gnx_finish_table left: v[4g + e] -> column cl + 8g + e of gA / gB (cl: the
+// tile-local column of g = 0, e = 0, the lane's 4 lh included), then SiLU.
+template <int R, typename V>
+__device__ __forceinline__ void gnx_normalise(const V& v, const float* gA, const float* gB, const int cl, const bool silu, float (&y)[R]) {
+#pragma unroll
+  for (int g = 0; g < R / 4; ++g) {
+    const float4 sa = *reinterpret_cast<const float4*>(gA + cl + 8 * g);
+    const float4 sb = *reinterpret_cast<const float4*>(gB + cl + 8 * g);
+    y[4 * g] = fmaf(v[4 * g], sa.x, sb.x); y[4 * g + 1] = fmaf(v[4 * g + 1], sa.y, sb.y);
+    y[4 * g + 2] = fmaf(v[4 * g + 2], sa.z, sb.z); y[4 * g + 3] = fmaf(v[4 * g + 3], sa.w, sb.w);
+  }
+  if (silu) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) y[r] = dv_silu(y[r]);
+  }
+}
 
 // Concatenated consumer (GnxParams sk_*; reference unet_1d_blocks.py:2085,2187 -> resnet.py:594: norm1 of an up-path resnet
 // runs over [h | skip]): this GEMM produces h, the skip tensor and ITS block statistics have been in memory since the down
@@ -99,7 +176,7 @@ __device__ __forceinline__ void gnx_finish_table(const GnxParams& gx, const GnxT
             w[k] = __hip_atomic_load(gx.xchg + (size_t)(bq * RB + rb) * ncb + cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           else {                                   // the skip's block: in memory since an earlier launch
             const float2 sv = reinterpret_cast<const float2*>(gx.sk_stat16)[(size_t)(bq * RB + rb) * ncs + (cb - ncb)];
-            w[k] = (unsigned long long)__float_as_uint(sv.x) | ((unsigned long long)__float_as_uint(sv.y) << 32);
+            w[k] = gnx_word(sv.x, sv.y);
           }
           ok = ok && w[k] != ~0ull;
         }
@@ -166,7 +243,7 @@ __device__ __forceinline__ void gnx_finish_table(const GnxParams& gx, const GnxT
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         y[e] = fmaf(v[e], sh.gA2[cl + e], sh.gB2[cl + e]);
-        if (gx.silu) y[e] = y[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[e]));
+        if (gx.silu) y[e] = dv_silu(y[e]);
       }
       auto put8 = [&](bf16_t* hi, bf16_t* lo, const float* x) {
         uint4 h, l;

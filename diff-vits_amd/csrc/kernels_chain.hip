@@ -59,9 +59,6 @@ constexpr int DEPTH = 6;                           // weight fragments (hi + lo:
 #endif
 constexpr int DEPTH_FF = DV_DEPTH_FF;              // k_chain_ff (one accumulator fragment per wave: registers to spare)
 
-__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ unsigned pk(float lo, float hi) { return dv_cvt_pk_bf16(lo, hi); }
-
 #ifndef DV_CHAIN_PFMODE
 // 0: ninth (L2-prefetch) wave wherever round 2 had it (some instantiations then spill at the 168-VGPR cap of a 576-thread
 // workgroup); 1: ninth wave only where the kernel fits 168 VGPRs, no prefetch elsewhere; 2: like 1, and the instantiations
@@ -1040,31 +1037,11 @@ __device__ __forceinline__ void chain_ff_stages(const ChainFFParams& p, char* co
     if (p.stats16) {
       // (padded row spaces: the utterance's last row block holds cnt < 32 frames that exist - the others stay out)
       const int Tv = p.Tv > 0 ? p.Tv : p.T, cnt = min(32, Tv - (m0 - (m0 / p.T) * p.T));
-      const bool r_ok = l31 < cnt;
-      float a1[2] = {0.f, 0.f}, a2[2] = {0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a1[r >> 3] += r_ok ? vv[r] : 0.f;
-      a1[0] = wave_sum64(a1[0]); a1[1] = wave_sum64(a1[1]);
-      const float inv_n = cnt == 32 ? 1.0f / 512.0f : 1.0f / (float)(16 * cnt);
-      const float mb[2] = {a1[0] * inv_n, a1[1] * inv_n};
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { const float dv = r_ok ? vv[r] - mb[r >> 3] : 0.f; a2[r >> 3] = fmaf(dv, dv, a2[r >> 3]); }
-      a2[0] = wave_sum64(a2[0]); a2[1] = wave_sum64(a2[1]);
-      if (lane < 2) {
-        const float2 val = make_float2(lane ? a1[1] : a1[0], lane ? a2[1] : a2[0]);
-        reinterpret_cast<float2*>(p.stats16)[(size_t)blockIdx.x * (C / 16) + wn * 2 + lane] = val;
-        if (gnx)       // for the other row blocks of the utterance: one 8-byte word (sum, M2), written through
-          __hip_atomic_store(p.gnx.xchg + (size_t)blockIdx.x * (C / 16) + wn * 2 + lane,
-                             (unsigned long long)__float_as_uint(val.x) | ((unsigned long long)__float_as_uint(val.y) << 32),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      const bool r_ok = l31 < cnt;                     // (the rows are NOT zeroed: both sums are masked, the raw rows stored)
+      gnx_block_stats<16, true>(p.stats16, p.gnx.xchg, vv, r_ok, r_ok, cnt, lane < 2, (size_t)blockIdx.x * (C / 16) + wn * 2 + lane, lane);
     }
     // (the statistics go out FIRST: the other row blocks of the utterance wait for them, nobody waits for these stores)
-    if (p.out) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        dv_st16(p.out + (size_t)m * C + nf + 8 * g, make_float4(vv[4 * g], vv[4 * g + 1], vv[4 * g + 2], vv[4 * g + 3]));
-    }
+    if (p.out) store_row(p.out, (size_t)m * C + nf, vv);
     if (p.out_hi) store_planes16(p.out_hi, p.out_lo, (size_t)m * C + nf - 4 * lh, lh, vv);   // 16-byte plane stores (dv_device.h)
     if (gnx) {
       // ---- the consumer's GroupNorm (+ SiLU) of this block's output, a concatenated skip tensor included (gnx_device.h):
@@ -1074,17 +1051,7 @@ __device__ __forceinline__ void chain_ff_stages(const ChainFFParams& p, char* co
       t.M = p.M; t.N = C; t.T_out = p.T; t.Tv_out = p.Tv > 0 ? p.Tv : p.T; t.m0 = m0; t.n0 = 0; t.bm = BM; t.bn = C; t.bq = m0 / p.T;
       gnx_finish_table<C>(p.gnx, t, s_gnx, tid, lane, wave, 4, [](int) {});
       float y[16];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 sa = *reinterpret_cast<const float4*>(s_gnx.gA + nf + 8 * g);
-        const float4 sb = *reinterpret_cast<const float4*>(s_gnx.gB + nf + 8 * g);
-        y[4 * g] = fmaf(vv[4 * g], sa.x, sb.x); y[4 * g + 1] = fmaf(vv[4 * g + 1], sa.y, sb.y);
-        y[4 * g + 2] = fmaf(vv[4 * g + 2], sa.z, sb.z); y[4 * g + 3] = fmaf(vv[4 * g + 3], sa.w, sb.w);
-      }
-      if (p.gnx.silu) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) y[r] = y[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[r]));
-      }
+      gnx_normalise(vv, s_gnx.gA, s_gnx.gB, nf, p.gnx.silu, y);
       store_planes16(p.gnx.y_hi, p.gnx.y_lo, (size_t)m * C + nf - 4 * lh, lh, y);
     }
   }

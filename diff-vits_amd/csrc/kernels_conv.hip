@@ -59,7 +59,6 @@ namespace {
 constexpr int BM = 64, BN = 64, NWV = 8, NT = 64 * NWV;
 constexpr int ROWS = BM + 2;                         // LDS rows of a chunk: the tile's 64, then row m0 + 64 (index 64), then row m0 - 1 (index 65)
 constexpr int CHP = ROWS * 128;                      // bytes of one 64-channel chunk of one plane
-__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
 struct BFrag { bf16x8 h, l; };
 constexpr int RED_BYTES = 2 * 4 * 2 * 4 * 64 * 16;      // k-quarter exchange: [column fragment][quarter][row fragment][4 column groups][64 lanes] float4
 
@@ -192,31 +191,13 @@ __device__ __forceinline__ void conv3_finish(const GemmParams& p, char* smem, co
   }
   if (live) {
     const size_t ob = (size_t)m * p.ldo + ncol;
-    if (p.out) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-        dv_st16(p.out + ob + 4 * lh + 8 * g, make_float4(vv[4 * g], vv[4 * g + 1], vv[4 * g + 2], vv[4 * g + 3]));
-    }
+    if (p.out) store_row(p.out, ob + 4 * lh, vv);
     if (p.out_hi) store_planes8(p.out_hi, p.out_lo, ob, lh, vv);
   }
   DV_C3TRACE(5);
-  if (p.stats16 && live) {                           // this wave's 32 x 16 block: (sum, squared deviations about its own mean)
-    float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) a1 += vv[r];
-    a1 = wave_sum64(a1);
-    const float mb = padded ? a1 / (float)(16 * min(32, p.Tv_out - tfr)) : a1 * (1.0f / 512.0f);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { const float dv = (!padded || m_ok) ? vv[r] - mb : 0.f; a2 = fmaf(dv, dv, a2); }
-    a2 = wave_sum64(a2);
-    if (lane == 0) {
-      const size_t e = (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol >> 4);
-      reinterpret_cast<float2*>(p.stats16)[e] = make_float2(a1, a2);
-      if (gnx_h)
-        __hip_atomic_store(p.gnx.xchg + e, (unsigned long long)__float_as_uint(a1) | ((unsigned long long)__float_as_uint(a2) << 32),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  if (p.stats16 && live)                             // this wave's 32 x 16 block statistics (gnx_device.h)
+    gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, !padded || m_ok, padded ? min(32, p.Tv_out - tfr) : 32, lane == 0,
+                              (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol >> 4));
   DV_C3TRACE(6);
   if (gnx_h) {
     GnxTile t;
@@ -225,18 +206,7 @@ __device__ __forceinline__ void conv3_finish(const GemmParams& p, char* smem, co
     gnx_finish_table<BN>(p.gnx, t, s_gnx, tid, lane, wave, NWV, [&](int) {});
     DV_C3TRACE(7);
     float y[8];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const int cl = e_wn * 32 + coff + 4 * lh + 8 * g;
-      const float4 sa = *reinterpret_cast<const float4*>(s_gnx.gA + cl);
-      const float4 sb = *reinterpret_cast<const float4*>(s_gnx.gB + cl);
-      y[4 * g] = fmaf(vv[4 * g], sa.x, sb.x); y[4 * g + 1] = fmaf(vv[4 * g + 1], sa.y, sb.y);
-      y[4 * g + 2] = fmaf(vv[4 * g + 2], sa.z, sb.z); y[4 * g + 3] = fmaf(vv[4 * g + 3], sa.w, sb.w);
-    }
-    if (p.gnx.silu) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) y[r] = y[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[r]));
-    }
+    gnx_normalise(vv, s_gnx.gA, s_gnx.gB, e_wn * 32 + coff + 4 * lh, p.gnx.silu, y);
     if (padded) {                                    // (rows that do not exist: zeros, like every producer of planes)
 #pragma unroll
       for (int r = 0; r < 8; ++r) y[r] = m_ok ? y[r] : 0.f;
@@ -615,35 +585,13 @@ __global__ __launch_bounds__(NT) void k_conv3u(const GemmParams p) {
   }
   if (live) {
     const size_t ob = (size_t)m * p.ldo + ncol0;
-    if (p.out) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        dv_st16(p.out + ob + 4 * lh + 8 * g, make_float4(vv[4 * g], vv[4 * g + 1], vv[4 * g + 2], vv[4 * g + 3]));
-    }
+    if (p.out) store_row(p.out, ob + 4 * lh, vv);
     if (p.out_hi) store_planes16(p.out_hi, p.out_lo, ob, lh, vv);
   }
   DV_C3TRACE(5);
-  if (p.stats16 && live) {
-    // per (32-row, 16-column) block: (sum, squared deviations from the block's own mean); registers 0-7 / 8-15 are the fragment's
-    // first / second 16 columns
-    float a1[2] = {0.f, 0.f}, a2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a1[r >> 3] += vv[r];
-    a1[0] = wave_sum64(a1[0]); a1[1] = wave_sum64(a1[1]);
-    const float inv = padded ? 1.0f / (float)(16 * min(32, p.Tv_out - tfr)) : (1.0f / 512.0f);
-    const float mb[2] = {a1[0] * inv, a1[1] * inv};
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { const float dv = (!padded || m_ok) ? vv[r] - mb[r >> 3] : 0.f; a2[r >> 3] = fmaf(dv, dv, a2[r >> 3]); }
-    a2[0] = wave_sum64(a2[0]); a2[1] = wave_sum64(a2[1]);
-    if (lane < 2) {
-      const size_t e = (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol0 >> 4) + lane;
-      const float2 val = make_float2(lane ? a1[1] : a1[0], lane ? a2[1] : a2[0]);
-      reinterpret_cast<float2*>(p.stats16)[e] = val;
-      if (gnx_h)
-        __hip_atomic_store(p.gnx.xchg + e, (unsigned long long)__float_as_uint(val.x) | ((unsigned long long)__float_as_uint(val.y) << 32),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  if (p.stats16 && live)                             // the fragment's two 32 x 16 block statistics (gnx_device.h)
+    gnx_block_stats<16, true>(p.stats16, p.gnx.xchg, vv, true, !padded || m_ok, padded ? min(32, p.Tv_out - tfr) : 32, lane < 2,
+                              (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol0 >> 4) + lane, lane);
   DV_C3TRACE(6);
   if (gnx_h) {
     GnxTile t;
@@ -652,18 +600,7 @@ __global__ __launch_bounds__(NT) void k_conv3u(const GemmParams p) {
     gnx_finish_table<BN>(p.gnx, t, s_gnx, tid, lane, wave, NWV, [&](int) {});
     DV_C3TRACE(7);
     float y[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int cl = e_wn * 32 + 4 * lh + 8 * g;
-      const float4 sa = *reinterpret_cast<const float4*>(s_gnx.gA + cl);
-      const float4 sb = *reinterpret_cast<const float4*>(s_gnx.gB + cl);
-      y[4 * g] = fmaf(vv[4 * g], sa.x, sb.x); y[4 * g + 1] = fmaf(vv[4 * g + 1], sa.y, sb.y);
-      y[4 * g + 2] = fmaf(vv[4 * g + 2], sa.z, sb.z); y[4 * g + 3] = fmaf(vv[4 * g + 3], sa.w, sb.w);
-    }
-    if (p.gnx.silu) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) y[r] = y[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[r]));
-    }
+    gnx_normalise(vv, s_gnx.gA, s_gnx.gB, e_wn * 32 + 4 * lh, p.gnx.silu, y);
     if (padded) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) y[r] = m_ok ? y[r] : 0.f;

@@ -51,8 +51,6 @@ extern "C" int dv_debug_ffs_trace(unsigned long long* host, int n_wg) {
 namespace {
 
 constexpr int NWV = 8, NT = 64 * NWV;
-__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ unsigned pk(float lo, float hi) { return dv_cvt_pk_bf16(lo, hi); }
 struct BFrag { bf16x8 h, l; };
 
 // RF = row fragments per workgroup: 2 (64 rows: C = 256 / 384) or 1 (32 rows: C = 512, where 64 rows of h3 alone would fill the LDS)
@@ -492,29 +490,11 @@ __global__ __launch_bounds__(NT) void k_ff_split(const FFSplitParams p) {
     DV_FTRACE(9);
     if (p.stats16) {   // this unit's 32 x 16 block: (sum, squared deviations about its own mean) over the frames that exist
       const int cnt = min(32, Tv - (m0 + f_rf * 32 - b_item * p.T));
-      float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) a1 += vv[r];
-      a1 = wave_sum64(a1);
-      const float mb = cnt == 32 ? a1 * (1.0f / 512.0f) : a1 / (float)(16 * cnt);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) { const float dv = m_ok ? vv[r] - mb : 0.f; a2 = fmaf(dv, dv, a2); }
-      a2 = wave_sum64(a2);
-      if (lane == 0) {
-        const size_t e = (size_t)((m0 >> 5) + f_rf) * (C >> 4) + f_hf;
-        reinterpret_cast<float2*>(p.stats16)[e] = make_float2(a1, a2);
-        if (p.gnx.xchg)    // for the other workgroups of the launch: one 8-byte word (sum, M2), written through
-          __hip_atomic_store(p.gnx.xchg + e, (unsigned long long)__float_as_uint(a1) | ((unsigned long long)__float_as_uint(a2) << 32),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, m_ok, cnt, lane == 0, (size_t)((m0 >> 5) + f_rf) * (C >> 4) + f_hf);
     }
     // (the statistics go out FIRST: other workgroups wait for them, nobody waits for these stores)
     const size_t ob = (size_t)f_m * C + f_hf * 16;
-    if (p.out) {
-#pragma unroll
-      for (int gg = 0; gg < 2; ++gg)
-        dv_st16(p.out + ob + 4 * lh + 8 * gg, make_float4(vv[4 * gg], vv[4 * gg + 1], vv[4 * gg + 2], vv[4 * gg + 3]));
-    }
+    if (p.out) store_row(p.out, ob + 4 * lh, vv);
     if (p.out_hi) store_planes8(p.out_hi, p.out_lo, ob, lh, vv);
   }
   DV_FTRACE(10);
@@ -525,19 +505,8 @@ __global__ __launch_bounds__(NT) void k_ff_split(const FFSplitParams p) {
     t.M = p.M; t.N = C; t.T_out = p.T; t.Tv_out = Tv; t.m0 = m0; t.n0 = s * G::BNF; t.bm = BM; t.bn = G::BNF; t.bq = b_item;
     gnx_finish_table<64>(p.gnx, t, s_gnx, tid, lane, wave, NWV, [](int) {});
     if (fin) {
-      const int cl0 = f_hfl * 16 + 4 * lh;                   // tile-local column of gg = 0, e = 0
       float y[8];
-#pragma unroll
-      for (int gg = 0; gg < 2; ++gg) {
-        const float4 sa = *reinterpret_cast<const float4*>(s_gnx.gA + cl0 + 8 * gg);
-        const float4 sb = *reinterpret_cast<const float4*>(s_gnx.gB + cl0 + 8 * gg);
-        y[4 * gg] = fmaf(vv[4 * gg], sa.x, sb.x); y[4 * gg + 1] = fmaf(vv[4 * gg + 1], sa.y, sb.y);
-        y[4 * gg + 2] = fmaf(vv[4 * gg + 2], sa.z, sb.z); y[4 * gg + 3] = fmaf(vv[4 * gg + 3], sa.w, sb.w);
-      }
-      if (p.gnx.silu) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) y[r] = y[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-y[r]));
-      }
+      gnx_normalise(vv, s_gnx.gA, s_gnx.gB, f_hfl * 16 + 4 * lh, p.gnx.silu, y);   // (tile-local column of gg = 0, e = 0)
       store_planes8(p.gnx.y_hi, p.gnx.y_lo, (size_t)f_m * C + f_hf * 16, lh, y);
     }
   }

@@ -64,8 +64,6 @@ extern "C" int dv_debug_qkv_trace(unsigned long long* host, int n_wg) {
 namespace {
 
 constexpr int NWV = 8, NT = 64 * NWV, BM = 64, BN = 64;   // (BM: the 64-row geometry - the only one MODE 2 runs at)
-__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ unsigned pk(float lo, float hi) { return dv_cvt_pk_bf16(lo, hi); }
 struct BFrag { bf16x8 h, l; };
 
 // rows of a row block: 64 where two planes of 64 resident rows and an exchange region fit the LDS (C <= 384), 32 at C = 512
