@@ -45,6 +45,10 @@ class MelCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("n_mels", C.c_int32), ("center", C.c_int32), ("log_clip", C.c_float)]
 
 
+class VocCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_mels", "dim", "intermediate", "n_layers", "n_fft", "hop")]
+
+
 MODEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p)
 
 # every symbol include/dvits_hip.h declares: (restype, argtypes)
@@ -97,6 +101,15 @@ SIGNATURES = {
     "dv_mel_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p]),
     "dv_mel_destroy": (None, [C.c_void_p]),
+    "dv_voc_create": (C.c_int, [C.POINTER(VocCfg), C.POINTER(C.c_void_p)]),
+    "dv_voc_destroy": (None, [C.c_void_p]),
+    "dv_voc_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "dv_voc_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "dv_voc_forward": (C.c_int, [C.c_void_p] * 6),
+    "dv_voc_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "dv_voc_probe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "dv_op_dwconv_ln": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 4),
+    "dv_op_istft_head": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 3),
     "dv_op_rel_attention": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_regulate_lengths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_op_regulate_sample": (C.c_int, [C.c_void_p] * 5 + [C.c_double] + [C.c_int32] * 4 + [C.c_void_p] * 4),

@@ -361,6 +361,25 @@ hipError_t launch_wn_store(const float* z, const float* noise, const int64_t* le
 // weight norm: w[n, :] = v[n, :] * (g[n] / ||v[n, :]||)
 hipError_t launch_wn_fold(const float* v, const float* g, float* w, int N, int per_row, hipStream_t st);
 
+// Vocoder kernels (kernels_voc.hip; the Vocos backbone and ISTFT head of voc.hip).  lengths [B] device or null (every row T frames);
+// a row whose length is outside [2, T] holds no frame.
+hipError_t voc_init();    // twiddle tables of k_istft_head (call outside stream capture)
+// mel [B, Cin, T] -> planes [B * T, Kp] (channels Cin .. Kp - 1 and padding rows zero) + keep [B * T]
+hipError_t launch_voc_pack(const float* mel, const int64_t* lengths, bf16_t* hi, bf16_t* lo, float* keep, int B, int Cin, int T, int Kp,
+                           hipStream_t st);
+// depthwise 7-tap convolution (w [C, 7], bias [C]; zero outside the utterance) + LayerNorm(gamma, beta, eps) of rows x [B * T, C]
+// -> fp32 y and / or split planes, padding rows zero.  C: a multiple of 64 up to 512 (dw7_ln_supported)
+bool dw7_ln_supported(int C);
+hipError_t launch_dw7_ln(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, const int64_t* lengths,
+                         int B, int T, int C, float eps, float* y, bf16_t* y_hi, bf16_t* y_lo, hipStream_t st);
+// fp32 [n] -> exact-erf GELU -> split planes (n % 4 == 0)
+hipError_t launch_voc_gelu(const float* in, bf16_t* hi, bf16_t* lo, int64_t n, hipStream_t st);
+// Wo[n, :] = gamma[n] W[n, :], bo = gamma b (W [N, K])
+hipError_t launch_voc_fold_gamma(const float* W, const float* b, const float* gamma, float* Wo, float* bo, int N, int K, hipStream_t st);
+// logits [B * T, ld >= 1026] (513 log-magnitudes | 513 phases) -> wave [B, (T - 1) * 256], samples [B]; window [1024]
+hipError_t launch_istft_head(const float* logits, int ld, const float* window, const int64_t* lengths, int B, int T, float* wave,
+                             int64_t* samples, hipStream_t st);
+
 // ---------------------------------------------------------------------------------------
 // Persistent per-XCD schedule (persist.hip): operation table in device memory, executed by one launch.
 // ---------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 // Ordering is by kernel boundary alone; nothing allocates, waits or hands over inside a launch.
 #include "../../include/dvits_hip.h"
 #include "dv_common.h"
+#include "fft512_device.h"
 
 #include <cmath>
 #include <new>
@@ -44,34 +45,6 @@ struct MelTables {
   const float* fb;         // [513, n_mels]
   const int2* band;        // [n_mels] (first, last) non-zero bin; (0, -1): empty band
 };
-
-__device__ __forceinline__ int zpad(int i) { return i + (i >> 3); }
-
-// b_k = sum_j a_j exp(-2 pi i j k / 8), in place
-__device__ __forceinline__ void dft8(float* __restrict__ r, float* __restrict__ i) {
-  const float h = 0.70710678118654752440f;
-  const float s0r = r[0] + r[4], s0i = i[0] + i[4], d0r = r[0] - r[4], d0i = i[0] - i[4];
-  const float s1r = r[1] + r[5], s1i = i[1] + i[5], d1r = r[1] - r[5], d1i = i[1] - i[5];
-  const float s2r = r[2] + r[6], s2i = i[2] + i[6], d2r = r[2] - r[6], d2i = i[2] - i[6];
-  const float s3r = r[3] + r[7], s3i = i[3] + i[7], d3r = r[3] - r[7], d3i = i[3] - i[7];
-  // even outputs: the 4-point transform of s
-  const float t0r = s0r + s2r, t0i = s0i + s2i, t1r = s0r - s2r, t1i = s0i - s2i;
-  const float t2r = s1r + s3r, t2i = s1i + s3i, t3r = s1r - s3r, t3i = s1i - s3i;
-  r[0] = t0r + t2r; i[0] = t0i + t2i;
-  r[4] = t0r - t2r; i[4] = t0i - t2i;
-  r[2] = t1r + t3i; i[2] = t1i - t3r;            // t1 - i t3
-  r[6] = t1r - t3i; i[6] = t1i + t3r;            // t1 + i t3
-  // odd outputs: the 4-point transform of (d0, d1 W8, d2 W8^2, d3 W8^3)
-  const float e1r = (d1r + d1i) * h, e1i = (d1i - d1r) * h;          // d1 (1 - i) / sqrt 2
-  const float e2r = d2i, e2i = -d2r;                                 // -i d2
-  const float e3r = (d3i - d3r) * h, e3i = (-d3r - d3i) * h;         // d3 (-1 - i) / sqrt 2
-  const float u0r = d0r + e2r, u0i = d0i + e2i, u1r = d0r - e2r, u1i = d0i - e2i;
-  const float u2r = e1r + e3r, u2i = e1i + e3i, u3r = e1r - e3r, u3i = e1i - e3i;
-  r[1] = u0r + u2r; i[1] = u0i + u2i;
-  r[5] = u0r - u2r; i[5] = u0i - u2i;
-  r[3] = u1r + u3i; i[3] = u1i - u3r;
-  r[7] = u1r - u3i; i[7] = u1i + u3r;
-}
 
 __global__ __launch_bounds__(MEL_THREADS) void k_log_mel(const float* __restrict__ wave, const int64_t* __restrict__ n_samples,
                                                          int n_max, float* __restrict__ out, int64_t* __restrict__ frames, int L_max,
@@ -247,12 +220,8 @@ extern "C" int dv_mel_create(const dv_mel_cfg* cfg, const float* window, const f
   float2* win2 = reinterpret_cast<float2*>(host.data() + o_win);
   float* fbh = reinterpret_cast<float*>(host.data() + o_fb);
   int2* band = reinterpret_cast<int2*>(host.data() + o_band);
-  const double two_pi = 6.283185307179586476925286766559;
-  for (int t = 0; t < 512; ++t) {
-    tw512[t] = make_float2((float)std::cos(two_pi * t / 512.0), (float)-std::sin(two_pi * t / 512.0));
-    tw1024[t] = make_float2((float)std::cos(two_pi * t / 1024.0), (float)-std::sin(two_pi * t / 1024.0));
-    win2[t] = make_float2(window[2 * t], window[2 * t + 1]);
-  }
+  fft512_fill_tables(tw512, tw1024);
+  for (int t = 0; t < 512; ++t) win2[t] = make_float2(window[2 * t], window[2 * t + 1]);
   for (int64_t i = 0; i < (int64_t)MEL_BINS * M; ++i) fbh[i] = fb[i];
   for (int m = 0; m < M; ++m) {
     int lo = 0, hi = -1;

@@ -262,6 +262,15 @@ def linear_beta_schedule(timesteps):
     return torch.linspace(scale * 0.0001, scale * 0.02, timesteps, dtype=torch.float64)
 
 
+def _decode_takes_lengths(vocos):
+    """True where `vocos.decode` has a `lengths` parameter (vocoder.Vocoder; not Vocos, not a test double)."""
+    import inspect
+    try:
+        return "lengths" in inspect.signature(vocos.decode).parameters
+    except (TypeError, ValueError):
+        return False
+
+
 class NaturalSpeech2(nn.Module):
     """Inference side of reference model3.NaturalSpeech2 (model3.py:955-1203): the diffusion model,
     the schedule buffers of __init__ (:976-1018, same names/values, so a reference checkpoint's buffers load) and
@@ -364,8 +373,10 @@ class NaturalSpeech2(nn.Module):
     @torch.no_grad()
     def sample_from_prior(self, content, refer=None, text_lengths=None, spec_lengths=None, vocos=None, sample_method="unipc", noise=None,
                           guidance_scale=1.0, negative_refer=None, negative_lengths=None, voices=None,
-                          known_mel=None, known_mask=None, known_noise=None, paste_known=True):
+                          known_mel=None, known_mask=None, known_noise=None, paste_known=True, frame_lengths=None):
         """(content, refer) -> (audio | None, mel): reference model3.py:1162-1203 after the `vits.infer` call.
+        frame_lengths int64 [B]: the mel frames of every row; handed to `vocos.decode(mel, lengths=...)` when that object's
+        decode accepts `lengths` (vocoder.Vocoder), ignored for any other vocoder.  None: the padded batch is decoded as ever.
         guidance_scale != 1: classifier-free guidance (model_wrapper(guidance_type='classifier-free'), dpm_solver.py:322-330)
         between the speaker prompt and `negative_refer` [B, 100, L'] with `negative_lengths` (None: all-zero encoder states
         under the prompt's mask) - on the HIP backend inside the one hipGraph, on the torch backend through the mirror's
@@ -503,7 +514,10 @@ class NaturalSpeech2(nn.Module):
         if vocos is None:
             return None, mel
         vocos.to(mel.device)
-        wav = vocos.decode(mel)
+        if frame_lengths is not None and _decode_takes_lengths(vocos):
+            wav = vocos.decode(mel, lengths=frame_lengths.to(mel.device))      # (vocoder.Vocoder: every row its own utterance)
+        else:
+            wav = vocos.decode(mel)
         if wav.ndim == 3:
             wav = wav.reshape(wav.shape[0], wav.shape[2])         # 'b 1 n -> b n'
         return wav, mel

@@ -61,6 +61,19 @@ def load_model(model_path, device, cfg, n_vocab=None, backend=None, aligner=Fals
     return model.to(device).eval()
 
 
+def load_vocoder(path, backend=None, precision="bf16x3"):
+    """A torch-saved Vocos state dict (the published names: vocoder.state_dict_names) -> `vocoder.Vocoder`, the object `sample`,
+    `sample_from_prior` and `synthesize` take as `vocos`.  A missing or unknown key is refused (feature_extractor.* is accepted
+    and ignored).  There is no from_pretrained and no network."""
+    from .vocoder import Vocoder
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(sd, dict) and "state_dict" in sd and "head.out.weight" not in sd:
+        sd = sd["state_dict"]
+    if not isinstance(sd, dict):
+        raise ValueError("%s is not a state dict" % (path,))
+    return Vocoder.from_state_dict(sd, backend=backend, precision=precision)
+
+
 def save_checkpoint(model, step, path):
     """The reference trainer's format (model3.py:1326-1333): {'step': int, 'model': state_dict}."""
     torch.save({"step": int(step), "model": model.state_dict()}, str(path))

@@ -109,6 +109,17 @@ typedef struct {
   float   log_clip;               /* floor under the logarithm of DV_MEL_LOG, > 0 (1e-7) */
 } dv_mel_cfg;
 
+/* Vocos vocoder (charactr/vocos-mel-24khz: ConvNeXt-1D backbone + ISTFT head).  The product is 100 mel channels -> dim 512,
+ * intermediate 1536, 8 layers, n_fft 1024, hop 256. */
+typedef struct {
+  int32_t n_mels;                 /* input channels (any; the input planes are padded to a multiple of 64) */
+  int32_t dim;                    /* C: a multiple of 64 up to 512 (k_dw7_ln) */
+  int32_t intermediate;           /* I: a multiple of 32 */
+  int32_t n_layers;
+  int32_t n_fft;                  /* 1024 */
+  int32_t hop;                    /* 256 */
+} dv_voc_cfg;
+
 typedef struct dv_unet dv_unet;
 typedef struct dv_plan dv_plan;
 typedef struct dv_penc dv_penc;
@@ -116,6 +127,7 @@ typedef struct dv_tenc dv_tenc;
 typedef struct dv_qenc dv_qenc;
 typedef struct dv_voice dv_voice;
 typedef struct dv_mel dv_mel;
+typedef struct dv_voc dv_voc;
 
 const char* dv_last_error(void);
 /* Library/version probe: returns e.g. "dvits_hip 0.1 gfx950". */
@@ -696,6 +708,32 @@ enum { DV_GN_STAT16 = 0, DV_GN_SLAB = 1, DV_GN_KSTAT16 = 2 };
 int dv_op_linear_gn(const float* x, const float* w, const float* b, const float* gamma, const float* beta, int32_t B, int32_t T,
                     int32_t Tp, int32_t K, int32_t C, int32_t G, float eps, int32_t route, float* y, float* stats,
                     uint16_t* y_norm_hi, uint16_t* y_norm_lo, void* stream);
+
+/* ---- vocoder: Vocos backbone + ISTFT head (csrc/voc.hip, csrc/kernels_voc.hip) --------
+ * mel [B, n_mels, T] (the denormalised log-mel) -> wave [B, (T - 1) * hop] float32 and samples [B] int64.  Ragged batches: with
+ * lengths [B] (int64, device) every row is its own utterance of L_b frames - filter taps read zeros at t < 0 and t >= L_b, the
+ * overlap-add and its envelope use L_b frames, row b holds n_b = (L_b - 1) * hop samples followed by exact zeros, samples[b] = n_b.
+ * A row with L_b < 2 or L_b > T is all zeros with samples[b] = 0.  lengths null: every row has T frames.
+ * State-dict names as the vocos package publishes them (backbone.*, head.out.*, head.istft.window). */
+int dv_voc_create(const dv_voc_cfg* cfg, dv_voc** out);     /* n_fft != 1024, hop != 256, dim / intermediate outside the kernels' range: DV_ERR_INVALID */
+void dv_voc_destroy(dv_voc* v);
+int dv_voc_set_weight(dv_voc* v, const char* name, const void* dev_ptr, const int64_t* shape, int32_t ndim);
+/* Packs the weights (once per weight set; gamma is folded into pwconv2) and plans the launches for B utterances of T frames.
+ * precision: DV_PREC_BF16X3 or DV_PREC_BF16 (the GEMMs; the depthwise convolution, the LayerNorms and the head are fp32 either way). */
+int dv_voc_prepare(dv_voc* v, int32_t B, int32_t T, int32_t precision);
+/* Enqueues the forward on `stream`: no allocation, no wait, capturable in a hipGraph. */
+int dv_voc_forward(dv_voc* v, const float* mel, const int64_t* lengths, float* wave, int64_t* samples, void* stream);
+int dv_voc_stats(dv_voc* v, int64_t* n_launch, double* flops);
+/* Kept intermediates [B, T, C] (prepare with DVITS_KEEP_INTERMEDIATES=1): embed, norm, l<i>.dwln, l<i>.act, l<i>.out, final, head. */
+int dv_voc_probe(dv_voc* v, const char* name, float* host_out, int64_t capacity, int64_t* dims);
+/* The vocoder's two kernels in isolation; both return after the stream has drained.
+ * dv_op_dwconv_ln: rows x [B * T, C] channels-last, w [C, 7], b / gamma / beta [C] -> LayerNorm(dwconv7(x)) as fp32 y and / or
+ * split planes y_hi / y_lo (any may be null, not all); C a multiple of 64 up to 512; 16-byte aligned pointers.
+ * dv_op_istft_head: logits [B * T, 1026] (513 log-magnitudes | 513 phases), window [1024] -> wave [B, (T - 1) * 256], samples [B]. */
+int dv_op_dwconv_ln(const float* x, const float* w, const float* b, const float* gamma, const float* beta, const int64_t* lengths,
+                    int32_t B, int32_t T, int32_t C, float eps, float* y, uint16_t* y_hi, uint16_t* y_lo, void* stream);
+int dv_op_istft_head(const float* logits, const float* window, const int64_t* lengths, int32_t B, int32_t T, float* wave,
+                     int64_t* samples, void* stream);
 
 #ifdef __cplusplus
 }
