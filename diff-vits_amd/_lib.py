@@ -101,6 +101,10 @@ SIGNATURES = {
     "dv_mel_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_void_p]),
     "dv_mel_destroy": (None, [C.c_void_p]),
+    "dv_resample_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "dv_resample_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p]),
+    "dv_resample_destroy": (None, [C.c_void_p]),
     "dv_voc_create": (C.c_int, [C.POINTER(VocCfg), C.POINTER(C.c_void_p)]),
     "dv_voc_destroy": (None, [C.c_void_p]),
     "dv_voc_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),

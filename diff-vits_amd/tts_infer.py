@@ -7,7 +7,8 @@ both are outside the diffusion hot path and their third-party dependencies are a
   * the size of the symbol table is taken from the checkpoint (`vits.enc_p.emb.weight`) unless `n_vocab` is passed;
   * `synthesize` takes batches whose reference audio is either a waveform tensor at 24 kHz (mel front-end of mel.py,
     pinned there to the fp64 restatement of its documented definition) or a ready log-mel prompt `[1, 100, L]`; a PATH needs torchaudio for decoding / resampling,
-    exactly as in the reference, and raises ImportError when it is missing.
+    exactly as in the reference, and raises ImportError when it is missing - unless `audio_backend="native"` asks for the package's
+    own WAV reader and sample-rate converter (audio.py; `save_wav` is the way out).
 Training-only checkpoint entries (the posterior encoder `vits.enc_q.*`) are not
 part of the inference model and are skipped when loading; every key the inference model owns must be present.
 `aligner=True` builds the posterior encoder for `VITS.align` (forced alignment): its entries are then the model's own and load.
@@ -79,35 +80,73 @@ def save_checkpoint(model, step, path):
     torch.save({"step": int(step), "model": model.state_dict()}, str(path))
 
 
-def refer_prompt(refer, device, mel_backend=None):
+def refer_prompt(refer, device, mel_backend=None, audio_backend=None, sample_rate=None, resample_backend=None):
     """Reference audio -> log-mel prompt [1, 100, L] (tts_infer.py:54-67).  `refer`: path, waveform [1, n] at 24 kHz,
-    or an already computed log-mel [1, 100, L].  mel_backend='hip' (opt-in): the native front-end (mel.py), one launch."""
+    or an already computed log-mel [1, 100, L].  mel_backend='hip' (opt-in): the native front-end (mel.py), one launch.
+    audio_backend='native' (opt-in): a path is decoded by audio.read_wav and converted from the file's rate to 24 kHz by
+    audio.Resample; the default needs torchaudio, as the reference does.  sample_rate: the rate of a waveform tensor (None: 24 kHz).
+    resample_backend='hip' (opt-in): the conversion on the native kernel (audio.py) - with mel_backend='hip' the route is upload,
+    k_resample, k_log_mel."""
+    if audio_backend not in (None, "native"):
+        raise ValueError("audio_backend must be None or 'native'")
     if isinstance(refer, (str, bytes)) or hasattr(refer, "__fspath__"):
-        try:
-            import torchaudio
-            import torchaudio.transforms as T
-        except ImportError as e:
-            raise ImportError("decoding a reference audio file needs torchaudio (as tts_infer.py:54-55); pass a 24 kHz "
-                              "waveform tensor or a log-mel prompt instead") from e
-        audio, sr = torchaudio.load(refer)
-        refer = T.Resample(sr, 24000)(audio)
+        if audio_backend == "native":
+            from .audio import read_wav
+            refer, sample_rate = read_wav(refer)
+        else:
+            try:
+                import torchaudio
+                import torchaudio.transforms as T
+            except ImportError as e:
+                raise ImportError("decoding a reference audio file needs torchaudio (as tts_infer.py:54-55); pass a 24 kHz "
+                                  "waveform tensor or a log-mel prompt instead") from e
+            audio, sr = torchaudio.load(refer)
+            refer = T.Resample(sr, 24000)(audio)
+            sample_rate = None
     refer = torch.as_tensor(refer)
     if refer.dim() == 3:
         return refer.to(device=device, dtype=torch.float32)
     if refer.dim() != 2:
         raise ValueError("reference audio must be [channels, samples] or a log-mel [1, 100, L], got %s" % (tuple(refer.shape),))
-    return reference_mel_prompt(refer.to(device=device, dtype=torch.float32), backend=mel_backend)
+    refer = refer.to(device=device, dtype=torch.float32)
+    if sample_rate is not None and int(sample_rate) != 24000:
+        from .audio import Resample
+        refer = Resample(int(sample_rate), 24000, backend=resample_backend)(refer)
+    return reference_mel_prompt(refer, backend=mel_backend)
 
 
-def recording_mels(waves, n_samples, device, mel_backend=None):
+def recording_mels(waves, n_samples, device, mel_backend=None, sample_rates=None, resample_backend=None):
     """A batch of recordings -> (y, y_lengths) for `VITS.align(..., y, y_lengths, ...)` and `NaturalSpeech2.enroll_voice`:
     waves [B, n_max] at 24 kHz (zero padded, or any content behind each row's samples), n_samples [B] -> the log-mel
     y [B, 100, 1 + n_max // 256] with zeros behind every row's own frames, and y_lengths int64 [B] = 1 + n_samples // 256.
     Every row is the mel of its own recording alone (reflect padding about its own end), on either backend;
-    mel_backend='hip' computes the batch in one launch."""
+    mel_backend='hip' computes the batch in one launch.
+    sample_rates (opt-in): the recordings' rate, one for the batch or one per row; every row is first converted to 24 kHz from its own
+    samples alone (audio.Resample), and n_max / n_samples above then read as the converted widths.  resample_backend='hip': that
+    conversion in one launch, its lengths handed to the mel kernel on the device."""
     waves = torch.as_tensor(waves).to(device=device, dtype=torch.float32)
     n_samples = torch.as_tensor(n_samples).to(device=device, dtype=torch.int64)
+    if sample_rates is not None:
+        from .audio import Resample
+        waves, n_samples = Resample(sample_rates, 24000, backend=resample_backend)(waves, n_samples)
     return reference_mel_prompt(waves, lengths=n_samples, backend=mel_backend)
+
+
+def save_wav(path, samples, out_rate=None, resample_backend=None, bits=16):
+    """Write what `sample` / `synthesize` return (24 kHz audio [B, n] - every row a channel of the file - or [n]) as a WAVE file
+    (audio.write_wav: PCM 16, or float32 with bits=32).  out_rate: convert from 24 kHz first (audio.Resample);
+    resample_backend='hip': on the native kernel (the samples go to the GPU and back)."""
+    from .audio import Resample, write_wav
+    x = torch.as_tensor(samples).detach().to(torch.float32)
+    if x.dim() == 1:
+        x = x[None, :]
+    rate = 24000
+    if out_rate is not None and int(out_rate) != 24000:
+        if resample_backend == "hip":
+            x = x.cuda()
+        x = Resample(24000, int(out_rate), backend=resample_backend)(x)
+        rate = int(out_rate)
+    write_wav(path, x.cpu(), rate, bits=bits)
 
 
 def synthesize(model, cfg, vocos, batchs, control_values=None, device="cuda", prompt_length="reference", mel_backend=None,

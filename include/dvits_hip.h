@@ -127,6 +127,7 @@ typedef struct dv_tenc dv_tenc;
 typedef struct dv_qenc dv_qenc;
 typedef struct dv_voice dv_voice;
 typedef struct dv_mel dv_mel;
+typedef struct dv_resample dv_resample;
 typedef struct dv_voc dv_voc;
 
 const char* dv_last_error(void);
@@ -512,6 +513,31 @@ typedef enum { DV_MEL_LOG = 1, DV_MEL_POWER2 = 2 } dv_mel_flags;
 int dv_mel_forward(dv_mel* h, const float* wave, const int64_t* n_samples, int32_t B, int32_t n_max, float* out, int64_t* frames,
                    int32_t L_max, int32_t flags, void* stream);
 void dv_mel_destroy(dv_mel* h);
+
+/* ---- sample-rate conversion: a ragged batch of recordings, each with its own rate pair, in one launch (csrc/kernels_resample.hip) ---- */
+
+/* orig / new_: HOST int32 [n_pairs], the rate pairs a call's rows choose from (Hz or any common unit; reduced by their gcd to o : n).
+ * Per pair the filter table of torchaudio.transforms.Resample's documented defaults (sinc_interp_hann, lowpass_filter_width 6,
+ * rolloff 0.99): base = min(o, n) * 0.99, width = ceil(6 o / base), K = 2 width + o, for phase p < n and tap j < K
+ *   t = clamp((-p / n + (j - width) / o) * base, -6, 6),  h[p][j] = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos(pi t / 12)^2 * base / o,
+ * computed in double on the host and rounded once to float32; orig == new: the delta h[0][width] = 1 (the identity, bit for bit).
+ * The device table keeps each phase's first non-zero tap, the count up to its last one and the taps between them (any table is
+ * handled).  n_pairs outside 1..64, a rate < 1, o or n above 1024 after reduction (the table is staged in LDS): DV_ERR_INVALID with
+ * the reason in dv_last_error. */
+int dv_resample_create(const int32_t* orig, const int32_t* new_, int32_t n_pairs, dv_resample** out);
+/* k_resample: wave float32 [B, n_max], n_samples DEVICE int64 [B], pair DEVICE int32 [B] (index into the handle's pairs; null: every
+ * row uses pair 0) -> out float32 [B, n_out_max], n_out DEVICE int64 [B].  n_out_max must be the largest ceil(n * n_max / o) over the
+ * handle's pairs (the host computes it; nothing is read back from the device); n_out[b] = ceil(n * n_samples[b] / o) of the row's own
+ * pair, written on the device so that it can be passed on as n_samples of dv_mel_forward without a host read.  Row b:
+ *   out[b][q n + p] = sum_j h[p][j] x[q o - width + j] over the phase's tap range in ascending j (float32, fmaf),
+ * x = 0 outside [0, n_samples[b]) - no sample at an index >= n_samples[b] is read.  Every element at or past n_out[b] is exactly 0.
+ * A row whose n_samples[b] is outside [0, n_max] or whose pair[b] is outside [0, n_pairs) is all zeros with n_out[b] = 0: a value for
+ * the caller to check, not a fault.  Null pointers (pair excepted), B outside 1..65535, n_max outside 1..2^30, a wrong n_out_max (or
+ * one beyond 2^32), misaligned pointers (4 bytes for wave / out / pair, 8 for n_samples / n_out): DV_ERR_INVALID before anything is
+ * launched.  One launch, no atomics, no allocation, no wait: capturable; two calls agree bit for bit. */
+int dv_resample_forward(dv_resample* h, const float* wave, const int64_t* n_samples, const int32_t* pair, int32_t B, int64_t n_max,
+                        float* out, int64_t n_out_max, int64_t* n_out, void* stream);
+void dv_resample_destroy(dv_resample* h);
 
 /* ---- single-operator entry points (parity tests of each kernel through the C ABI) ---- */
 
