@@ -1,9 +1,15 @@
 // Internal declarations shared by the kernel translation units and the engine.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 typedef unsigned short bf16_t;   // raw bfloat16 bits
+
+// The kernels with large argument blocks open with an `asm volatile("" :: "s"(p.a), "s"(p.b), ...)` list that requests the block's
+// 64-byte lines together (see k_gemm).  Which lines a list reaches depends on the struct's layout, so every list is pinned by a
+// static_assert on sizeof and on dv_arg_lines(offsetof(...) of each named member): the bitmask of lines that hold them.
+template <typename... O> constexpr unsigned dv_arg_lines(O... off) { return (0u | ... | (1u << (off / 64))); }
 
 // ---------------------------------------------------------------------------------------
 // Implicit-GEMM parameters.  One launch computes
@@ -25,6 +31,38 @@ struct GemmSeg {
   int nkt;             // k-tiles of this segment = taps * (c0+c1) / BK   (set by the launcher)
 };
 
+// ---------------------------------------------------------------------------------------
+// In-launch hand-overs: launches whose workgroups wait for one another inside the kernel (the GroupNorm exchange of
+// GnxParams, the all-gather of h in k_qkv_split, the partial sums of k_ff_split).  Every such wait is handover_wait
+// (handover_device.h): bounded by spin_max, given up early once any launch has lost the run, and reported in ONE record
+// that the host reads after the run (dv_unet_health / dv_unet_handover_status; engine.py re-plans without hand-overs and
+// repeats the run).
+// ---------------------------------------------------------------------------------------
+struct HandoverParams {
+  unsigned long long* words;     // null: off.  This launch's exchange words of the pool, EMPTY (all ones) before the launch
+  unsigned* status;              // the HandoverStatus record (host memory, written through)
+  int spin_max;                  // polls before a wait gives up (default 1 << 18, ~0.4 s; tests force time-outs with -1 / 1)
+};
+// What a wait that gave up leaves behind.  handover_report is its only writer: the payload first, then timed_out.
+struct HandoverStatus {
+  unsigned timed_out;            // 1: a wait gave up (the run's results are invalid); cleared by dv_unet_handover_reset
+  unsigned id;                   // low 32 bits of the launch's HandoverParams::words
+  unsigned wg;                   // blockIdx.x of the reporting workgroup
+  unsigned code;                 // HandoverCode
+  unsigned detail;               // lanes of the reporting wave whose words were missing; HO_QKV_XCD: the XCC id the reporter ran on
+  unsigned pad_[11];
+};
+static_assert(sizeof(HandoverStatus) == 64, "the status record is one 64-byte host allocation");
+enum HandoverCode : unsigned {
+  HO_GNX_GROUP_END = 0x80,       // values below: the GroupNorm group a gnx_finish_table wait was reducing
+  HO_QKV_H = 0xc1,               // k_qkv_split: the all-gather of h
+  HO_QKV_XCD = 0xc2,             // k_qkv_split: a partner of the XCD-local form ran on another XCD (no wait gave up)
+  HO_QKV_O = 0xc3,               // k_qkv_split: the attention output of the cross-attention form
+  HO_FF_PARTIAL = 0xff5,         // k_ff_split: the partial sums of a row block
+};
+constexpr int DV_GNX_MAX_GROUPS = 64;   // groups of an in-launch GroupNorm (gemm_gnx_plan / chain_ff_gnx_plan / ff_split_gnx_plan refuse more)
+static_assert(DV_GNX_MAX_GROUPS <= HO_GNX_GROUP_END, "a group index must not read as a named code");
+
 // GroupNorm of the GEMM's OWN output finished in its epilogue (gemm_tile.h "GNX"): every workgroup publishes the
 // 32x16-block statistics of its tile in an exchange buffer (8-byte words, written through), polls the words of its
 // groups until all of the utterance's tiles have published (EMPTY = all ones; the first kernel of every forward resets
@@ -34,12 +72,10 @@ struct GemmSeg {
 // sequence number, and a counter round trip sits on every workgroup's critical path.  ALL workgroups of the launch must
 // be resident at once: launch_gemm refuses grids larger than the device's CU count (gemm_gnx_plan()).
 struct GnxParams {
-  unsigned long long* xchg;      // null: off.  [M / 32][N / 16] (sum | M2 << 32) words of THIS op, EMPTY before the launch
-  unsigned* status;              // set to 1 if a wait timed out (results invalid; the host checks after the run)
+  HandoverParams ho;             // words: [M / 32][N / 16] (sum | M2 << 32) of THIS op
   const float* gamma; const float* beta;   // [N]
   const float* tscale; const float* tshift; int ld_t;   // temb scale / shift rows [B, ld_t] or null
   int groups; float eps; int silu;
-  int spin_max;                  // polls before a wait gives up (default 1 << 18, ~0.4 s; tests force time-outs with 1)
   bf16_t* y_hi; bf16_t* y_lo;    // normalised split planes [M, N]
   // Concatenated consumer (norm1 of an up-path resnet over [this GEMM's output | skip], reference unet_1d_blocks.py:2085,2187):
   // sk_c > 0 skip channels; gamma / beta then hold N + sk_c entries and `groups` are those of the concatenation.  The skip's
@@ -118,6 +154,12 @@ struct GemmParams {
   int trace;                    // development build (make trace): this launch stamps its phases (gemm_tile.h DV_TRACE)
 #endif
 };
+// the members the lists of k_gemm and the convolution kernels name: every one of GemmParams' nine lines
+constexpr unsigned DV_GEMM_ARG_LINES =
+    dv_arg_lines(offsetof(GemmParams, seg[0].a0_hi), offsetof(GemmParams, seg[1].a0_hi), offsetof(GemmParams, seg[1].pad), offsetof(GemmParams, T_in),
+                 offsetof(GemmParams, w_hi), offsetof(GemmParams, M), offsetof(GemmParams, res), offsetof(GemmParams, out_hi),
+                 offsetof(GemmParams, zero_page), offsetof(GemmParams, ln_u), offsetof(GemmParams, gnx.ho.words), offsetof(GemmParams, gnx.y_hi),
+                 offsetof(GemmParams, xcd_n), offsetof(GemmParams, xcd_inv_tn));
 inline unsigned gemm_tout_magic(int T_out) { return T_out <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)T_out - 1) / (unsigned)T_out); }
 // exchange words a GNX GEMM needs (M / 32 * N / 16), or 0 if launch_gemm would refuse it (tile shape vs T_out / groups,
 // more workgroups than `n_cu` compute units, unsupported epilogue)
@@ -189,8 +231,8 @@ struct ChainParams {
   // repeating stage 1 - for launches with fewer row blocks than CUs (every workgroup streams the weights it multiplies)
   int nsplit;
   // k_qkv_split (kernels_qkv.hip: amode 1 with sa_*, 64-row blocks, the output columns split over C / 64 workgroups per row block):
-  // qkv_split_flags(p) exchange words, EMPTY (all ones) before the launch; time-out flag / bound of the wait (GnxParams)
-  unsigned long long* qs_flags; unsigned* qs_status; int qs_spin;
+  // qkv_split_flags(p) exchange words
+  HandoverParams ho;
   bf16_t* qs_o_hi; bf16_t* qs_o_lo;   // MODE 2 (with xa_*): scratch planes [M, C] of the attention output (handed over between the slices)
   int qs_xcd;                    // internal (launcher): 1 = the slices of a row block share an XCD and hand h over through its L2
 };
@@ -213,7 +255,7 @@ struct ChainFFParams {
   const float* res;                               // block input [M, C] fp32
   float* out; float* stats16;                     // [M, C] fp32 (null: nobody reads it); [M/32, C/16, 2] or null
   bf16_t* out_hi; bf16_t* out_lo;                 // optional split planes of the output
-  GnxParams gnx;                                  // xchg != null: the consumer's GroupNorm is finished by this launch (gnx_device.h)
+  GnxParams gnx;                                  // ho.words != null: the consumer's GroupNorm is finished by this launch (gnx_device.h)
 };
 bool chain_ff_supported(const ChainFFParams& p, int precision);
 // exchange words the in-launch GroupNorm of k_chain_ff needs (gnx.groups / gnx.sk_c set), 0: not possible (see gemm_gnx_plan)
@@ -254,9 +296,8 @@ struct FFSplitParams {
   float* out; float* stats16;                     // [M, C] fp32 (null: nobody reads it); [M/32, C/16, 2] or null
   bf16_t* out_hi; bf16_t* out_lo;                 // optional split planes of the output
   float* xbuf;                                    // partial sums: ff_split_xbuf_floats(M, C, nspl) floats of scratch
-  unsigned long long* flags;                      // (M / rows) * nspl * 8 exchange words (one per wave), EMPTY (all ones) before the launch
-  unsigned* status; int spin_max;                 // time-out flag / bound of the waits (GnxParams)
-  GnxParams gnx;                                  // xchg != null: the consumer's GroupNorm is finished by this launch
+  HandoverParams ho;                              // (M / rows) * nspl * 8 exchange words (one per wave)
+  GnxParams gnx;                                  // ho.words != null: the consumer's GroupNorm is finished by this launch
 };
 bool ff_split_supported(const FFSplitParams& p, int precision);
 size_t ff_split_xbuf_floats(int M, int C, int nspl, int rows);

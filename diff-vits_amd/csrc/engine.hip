@@ -172,7 +172,7 @@ struct dv_unet {
   static constexpr size_t GNX_POOL = (size_t)1 << 19;   // 8-byte words (4 MiB)
   unsigned long long* gnx_pool = nullptr;
   size_t gnx_words = 0;                      // words in use by the prepared schedule
-  unsigned* gnx_status = nullptr;
+  HandoverStatus* gnx_status = nullptr;
   int gnx_ops = 0;
   bool exclusive = true;                     // false: other streams may run kernels beside this handle's (no in-launch waits)
   std::vector<OpFn> step_ops, cond_ops;
@@ -668,12 +668,15 @@ struct Builder {
   bool gnx_cat_on = [] { const char* e = getenv("DVITS_GNX_CONCAT"); return !(e && e[0] == '0'); }();
   // what every in-launch hand-over needs: all workgroups of the launch co-resident, nothing else on the device beside them
   bool handover_ok() const { return gnx_on && u->exclusive && !arena.exact && n_cu > 0; }
-  // `n` exchange words of the pool for one launch's in-launch hand-over (the caller has checked that they fit)
-  struct Handover { unsigned long long* flags; unsigned* status; };
-  Handover handover(size_t n) {
-    Handover h{dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used,
-               dry ? reinterpret_cast<unsigned*>(0x1000) : u->gnx_status};
-    gnx_used += (n + 1) & ~(size_t)1;
+  // the pool still holds `launches` hand-overs of `n` exchange words each (every grant is rounded up to an even word count)
+  static size_t handover_words(size_t n) { return (n + 1) & ~(size_t)1; }
+  bool handover_fits(size_t n, int launches = 1) const { return gnx_used + (size_t)launches * handover_words(n) <= dv_unet::GNX_POOL; }
+  // `n` exchange words of the pool for one launch's in-launch hand-over (the caller has checked handover_fits), the status
+  // record and the bound of its waits
+  HandoverParams handover(size_t n) {
+    HandoverParams h{dry ? reinterpret_cast<unsigned long long*>(0x1000) : u->gnx_pool + gnx_used,
+                     dry ? reinterpret_cast<unsigned*>(0x1000) : &u->gnx_status->timed_out, gnx_spin};
+    gnx_used += handover_words(n);
     if (!dry) { u->gnx_words = gnx_used; u->gnx_ops++; }
     return h;
   }
@@ -695,7 +698,7 @@ struct Builder {
       t.sk_buf = reinterpret_cast<float*>(0x1000); t.sk_ticket = reinterpret_cast<unsigned*>(0x1000);
     }
     const int nw = gemm_gnx_plan(t, n_cu);
-    if (nw <= 0 || gnx_used + (size_t)nw > dv_unet::GNX_POOL) return false;
+    if (nw <= 0 || !handover_fits((size_t)nw)) return false;
     g.gnx = t.gnx;
     gnx_fill(g.gnx, nw, g.M, g.N, pre, eps, tscale, tshift, ld_t, silu, y, skip, sk_y, sk_raw);
     return true;
@@ -705,9 +708,7 @@ struct Builder {
                 bool silu, Planes* y, const Act* skip, Planes* sk_y, Planes* sk_raw) {
     gx.gamma = W(pre + ".weight"); gx.beta = W(pre + ".bias"); gx.eps = eps;
     gx.tscale = tscale; gx.tshift = tshift; gx.ld_t = ld_t; gx.silu = silu ? 1 : 0;
-    gx.spin_max = gnx_spin;
-    const Handover h = handover((size_t)nw);
-    gx.xchg = h.flags; gx.status = h.status;
+    gx.ho = handover((size_t)nw);
     *y = alloc_planes((size_t)M * N);
     gx.y_hi = y->hi; gx.y_lo = y->lo;
     if (skip) {
@@ -750,7 +751,7 @@ struct Builder {
     fp.gnx.groups = u->cfg.norm_num_groups;
     fp.gnx.sk_c = cat ? nn.skip.C : 0;
     const int nw = ff_gnx_plan(fp, n_cu);
-    if (nw <= 0 || gnx_used + (size_t)nw > dv_unet::GNX_POOL) { fp.gnx = GnxParams{}; return false; }
+    if (nw <= 0 || !handover_fits((size_t)nw)) { fp.gnx = GnxParams{}; return false; }
     gnx_fill(fp.gnx, nw, fp.M, fp.C, nn.pre, nn.eps, nullptr, nullptr, 0, nn.silu, y, cat ? &nn.skip : nullptr, sy, nn.raw ? sr : nullptr);
     return true;
   }
@@ -834,7 +835,7 @@ struct Builder {
       // (" -fp32": no fp32 output - the tensor leaves as its raw planes, or, with no planes either, normalised only)
       snprintf(buf, sizeof(buf), "M=%d N=%d K=%d taps=%d nseg=%d epi=%d stride=%d up=%d%s%s%s%s", g.M, g.N, k_real, g.seg[0].taps,
                g.nseg, g.epi, g.stride, g.up_mode, (g.stats || g.stats16) ? " +stats" : "", c3 ? " resident" : "",
-               g.gnx.xchg ? " +gnx" : "", (g.gnx.xchg && !g.out) ? (g.out_hi ? " -fp32" : " -fp32 normonly") : "");
+               g.gnx.ho.words ? " +gnx" : "", (g.gnx.ho.words && !g.out) ? (g.out_hi ? " -fp32" : " -fp32 normonly") : "");
       cur_desc = buf;
     }
     u->flops += dry ? 0.0 : cur_flops;
@@ -860,7 +861,7 @@ struct Builder {
       if (&ops == &u->cond_ops) u->cond_gemms.push_back(gp);
       dv_unet* uu = u;
       emit(ops, [gp, p, uu](hipStream_t st) {
-        if (!uu->io.tp_base || !gp->gnx.xchg || !gp->gnx.tscale) return launch_gemm(*gp, p, st);
+        if (!uu->io.tp_base || !gp->gnx.ho.words || !gp->gnx.tscale) return launch_gemm(*gp, p, st);
         GemmParams g2 = *gp;                 // this evaluation's rows of the batched time_emb_proj table
         g2.gnx.tscale = uu->io.tp_base + (gp->gnx.tscale - uu->temb.tproj_arena);
         g2.gnx.tshift = uu->io.tp_base + (gp->gnx.tshift - uu->temb.tproj_arena);
@@ -1144,8 +1145,7 @@ struct Builder {
   // words fit; false (nothing planned) if the kernel does not take `cp`.
   bool qkv_split(std::vector<OpFn>& ops, ChainParams cp, std::string desc, double extra_flops = 0.0) {
     if (!qkv_split_supported(cp, prec)) return false;
-    const Handover h = handover((size_t)qkv_split_flags(cp));
-    cp.nsplit = 1; cp.qs_flags = h.flags; cp.qs_status = h.status; cp.qs_spin = gnx_spin;
+    cp.nsplit = 1; cp.ho = handover((size_t)qkv_split_flags(cp));
     const int pr = prec;
     emit_launch(ops, "chain", chain_flops(cp) + extra_flops, std::move(desc), [cp, pr](hipStream_t st) { return launch_qkv_split(cp, pr, st); });
     return true;
@@ -1194,7 +1194,7 @@ struct Builder {
     LnIn l3;
     // (C = 512: both split launches' exchange words must still fit the pool - else one launch per GEMM, the GroupNorm by k_gn_apply)
     const bool split32 = !chain_ok(b.Tp, C) && split32_ok(b.Tp, C) &&
-                         gnx_used + 2 * (((size_t)split32_wgs(b.Tp, C) + 1) & ~(size_t)1) <= dv_unet::GNX_POOL;
+                         handover_fits((size_t)split32_wgs(b.Tp, C), 2);
     if ((chain_ok(b.Tp, C) || split32) && x.stat16) {
       if (!(frag(b.w_in) && frag(b.w_qkv) && frag(b.w_o1) && frag(b.w_q2))) return Act{};
       float* h = nullptr;
@@ -1238,7 +1238,7 @@ struct Builder {
     // by it; the C = 512 launches, which that switch does not reach, read "[n wg / 32 rows]")
     const int q_rows = M * (C / 64) / n_qflags;      // rows of a row block (64; 32 at C = 512)
     const bool split = (qkv_split_on || !chained) && C >= qkv_split_min_c && C <= qkv_split_max_c && sa_frag && handover_ok() && !autotune_on() &&
-                       n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL &&   // (one round of workgroups: at B = 16 - 384 / 512 of them - the 32-row chain is the faster one, 4.09 vs 4.19 ms per forward)
+                       n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && handover_fits((size_t)n_qflags) &&   // (one round of workgroups: at B = 16 - 384 / 512 of them - the 32-row chain is the faster one, 4.09 vs 4.19 ms per forward)
                        qkv_split(ops, cp, strf(chained ? "norm+proj_in+LN+q|Kfrag|Vfrag (%d wg / %d rows) M=%d C=%d N2=%d" : "norm+proj_in+LN+q|Kfrag|Vfrag [%d wg / %d rows] M=%d C=%d N2=%d", C / 64, q_rows, M, C, 3 * C));
     if (!split && !chained) { err = "the column-split block head refused a shape its planner admitted"; return Planes{}; }
     if (!split) chain(ops, cp, sa_frag ? "norm+proj_in+LN+q|Kfrag|Vfrag" : "norm+proj_in+LN+qkv");
@@ -1313,7 +1313,7 @@ struct Builder {
     const bool chained = chain_ok(b.Tp, C);          // (C = 512: no row-block chain - the 32-row split launch, or one launch per GEMM)
     const int q_rows = M * (C / 64) / n_qflags;
     const bool split = (qkv_split_on || !chained) && C >= qkv_split_min_c && C <= qkv_split_max_c && handover_ok() && !autotune_on() &&
-                       n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && gnx_used + (size_t)n_qflags <= dv_unet::GNX_POOL &&
+                       n_qflags <= n_cu && n_qflags >= qkv_split_min_wg && handover_fits((size_t)n_qflags) &&
                        qkv_split(ops, cp, strf(chained ? "to_out+res+LN+to_q (%d wg / %d rows) M=%d C=%d N2=%d" : "to_out+res+LN+to_q [%d wg / %d rows] M=%d C=%d N2=%d", C / 64, q_rows, M, C, C));
     if (!split && !chained) {
       release(q2); release(h2);
@@ -1372,7 +1372,7 @@ struct Builder {
     const int n_wg = (M / 64) * (C / 64);
     bool split_xa = qkv_split_on && qkv_xa_on && C >= qkv_xa_min_c && handover_ok() && !autotune_on() &&
                     Tp % 64 == 0 && (M / 64) % 8 == 0 && n_wg <= n_cu && n_wg >= qkv_split_min_wg && u->cfg.num_heads == 8 &&
-                    gnx_used + (size_t)2 * n_wg <= dv_unet::GNX_POOL;
+                    handover_fits((size_t)2 * n_wg);
     Planes oxa;
     if (split_xa) {
       oxa = alloc_planes((size_t)M * C);
@@ -1478,7 +1478,7 @@ struct Builder {
     if (xa_ff.set || (one_launch && chain_ff_on && chain_ff_supported(cf, prec))) return ff_launch(ops, b, cf, h3, l3, want_planes);
     else if (one_launch && ff_split_on && handover_ok() && !autotune_on() && (C == 256 || C == 384 || C == 512) &&
              ff_split_supported(fs, prec) && (ff_wg <= n_cu || gemm_handover_rounds()) && ff_wg >= ff_split_min_wg &&
-             gnx_used + n_flags <= dv_unet::GNX_POOL)
+             handover_fits(n_flags))
       return ff_launch(ops, b, fs, h3, l3, want_planes);
     else return xf_ff_gemms(ops, b, h3, l3, want_planes);
   }
@@ -1512,14 +1512,13 @@ struct Builder {
     fp.wm_hi = w_m->fhi; fp.wm_lo = w_m->flo; fp.bm = w_m->bias;
     fp.res = b.x.p; fp.out = out.p; fp.stats16 = out.stat16;
     if constexpr (split) {
-      const Handover ho = handover((size_t)(M / fp.rows) * fp.nspl * 8);
-      fp.flags = ho.flags; fp.status = ho.status; fp.spin_max = gnx_spin;
+      fp.ho = handover((size_t)(M / fp.rows) * fp.nspl * 8);
       fp.xbuf = alloc(ff_split_xbuf_floats(M, C, fp.nspl, fp.rows));
     }
     if (want_planes) out_planes(fp, out);
     offer_next(fp, out);
     const double flops = 2.0 * (double)M * C * (8.0 * C + 5.0 * C);
-    const char* gnx = fp.gnx.xchg ? (fp.out ? "+gnx" : "+gnx-fp32") : "";   // ("-fp32": the output leaves as planes alone)
+    const char* gnx = fp.gnx.ho.words ? (fp.out ? "+gnx" : "+gnx-fp32") : "";   // ("-fp32": the output leaves as planes alone)
     const int pr = prec;
     if constexpr (split) {
       emit_launch(ops, "chain", flops, strf("LN+GEGLU+ffproj+res%s (%d wg / %d rows) M=%d C=%d", gnx, fp.nspl, fp.rows, M, C),
@@ -1691,8 +1690,8 @@ struct Builder {
         u->gnx_pool = reinterpret_cast<unsigned long long*>(z);
       }
       if (!u->gnx_status) {
-        if (hipHostMalloc((void**)&u->gnx_status, 64, hipHostMallocMapped) != hipSuccess) return dv_fail(DV_ERR_HIP, "hipHostMalloc(status word) failed");
-        *u->gnx_status = 0;
+        if (hipHostMalloc((void**)&u->gnx_status, sizeof(HandoverStatus), hipHostMallocMapped) != hipSuccess) return dv_fail(DV_ERR_HIP, "hipHostMalloc(status word) failed");
+        *u->gnx_status = HandoverStatus{};
       }
       if (!u->sk_tickets) {      // (fused split-K pairs and the two-workgroup cross-attention chain share them: both leave zeros behind)
         void* z = nullptr;
@@ -2484,9 +2483,10 @@ extern "C" int dv_unet_bind_voices(dv_unet* u, const int32_t* rows, dv_voice* co
   return DV_OK;
 }
 
-// In-kernel hand-over health (GnxParams): *n_ops = GEMMs of the schedule that finish their consumer's GroupNorm in the
-// epilogue; *timed_out = 1 if any such launch since prepare gave up waiting (its results are invalid).  No device
-// synchronisation: the flag lives in host memory the kernels write through; complete after the stream has drained.
+// In-kernel hand-over health (HandoverParams): *n_ops = launches of the schedule with an in-launch hand-over - one per
+// producer that finishes its consumer's GroupNorm in the epilogue, one more per k_qkv_split and k_ff_split launch;
+// *timed_out = 1 if any such launch since prepare gave up waiting (its results are invalid).  No device
+// synchronisation: the record lives in host memory the kernels write through; complete after the stream has drained.
 extern "C" int dv_unet_set_exclusive(dv_unet* u, int32_t exclusive) {
   if (!u) return dv_fail(DV_ERR_INVALID, "dv_unet_set_exclusive: null handle");
   if (u->exclusive != (exclusive != 0)) { u->exclusive = exclusive != 0; u->prepared = false; }   // takes effect at the next prepare
@@ -2498,28 +2498,39 @@ extern "C" int dv_unet_set_exclusive(dv_unet* u, int32_t exclusive) {
 extern "C" int dv_unet_handover_reset(dv_unet* u) {
   if (!u) return dv_fail(DV_ERR_INVALID, "dv_unet_handover_reset: null handle");
   HIPCHK(hipDeviceSynchronize());
-  if (u->gnx_status) { for (int i = 0; i < 8; ++i) ((volatile unsigned*)u->gnx_status)[i] = 0; }
+  if (u->gnx_status) { *u->gnx_status = HandoverStatus{}; __atomic_thread_fence(__ATOMIC_SEQ_CST); }   // (after the synchronise: no kernel is writing)
   return DV_OK;
 }
 extern "C" int dv_unet_handover_status(dv_unet* u, int32_t* n_ops, int32_t* timed_out) {
   if (!u || !u->prepared) return dv_fail(DV_ERR_STATE, "dv_unet_handover_status before prepare");
   if (n_ops) *n_ops = u->gnx_ops;
-  if (timed_out) *timed_out = u->gnx_status ? (int32_t)*(volatile unsigned*)u->gnx_status : 0;
+  if (timed_out) *timed_out = u->gnx_status ? (int32_t)((volatile HandoverStatus*)u->gnx_status)->timed_out : 0;
   return DV_OK;
 }
+// What the one record says (HandoverStatus, written by handover_report): decoded by its code.
 int dv_unet_health(const dv_unet* u) {
-  if (u->gnx_status && *(volatile unsigned*)u->gnx_status) {
-    const volatile unsigned* st = u->gnx_status;
+  const volatile HandoverStatus* st = u->gnx_status;
+  if (!st || !st->timed_out) return DV_OK;
+  const unsigned id = st->id, wg = st->wg, code = st->code, detail = st->detail;
+  if (code < HO_GNX_GROUP_END) {                     // a GroupNorm wait: `code` is the group
     const GemmParams* hit = nullptr;
     for (const auto& gp : u->gemm_store)
-      if (gp->gnx.xchg && (unsigned)(size_t)gp->gnx.xchg == st[1]) hit = gp.get();
+      if (gp->gnx.ho.words && (unsigned)(size_t)gp->gnx.ho.words == id) hit = gp.get();
     return dv_fail(DV_ERR_HIP, "an earlier launch's in-kernel GroupNorm hand-over timed out (its results are invalid): GEMM M=%d N=%d "
                                "T_out=%d taps=%d split-K=%d, workgroup %u, group %u, %u entries missing; DVITS_GNX=0 runs GroupNorm "
                                "as separate launches",
                    hit ? hit->M : -1, hit ? hit->N : -1, hit ? hit->T_out : -1, hit ? hit->seg[0].taps : -1,
-                   hit ? (hit->sk_buf ? hit->sk_split : 0) : -1, st[2], st[3], st[4]);
+                   hit ? (hit->sk_buf ? hit->sk_split : 0) : -1, wg, code, detail);
   }
-  return DV_OK;
+  if (code == HO_QKV_XCD)
+    return dv_fail(DV_ERR_HIP, "an earlier launch's in-kernel hand-over timed out (its results are invalid): k_qkv_split, workgroup %u on "
+                               "XCD %u found a partner of its row block on another XCD (the XCD-local form expects workgroup b on XCD "
+                               "b %% 8); DVITS_GNX=0 plans no in-launch hand-over", wg, detail);
+  const char* what = code == HO_QKV_H ? "k_qkv_split, the all-gather of h"
+                     : code == HO_QKV_O ? "k_qkv_split, the attention output of its row block"
+                     : code == HO_FF_PARTIAL ? "k_ff_split, the partial sums of its row block" : "unknown code";
+  return dv_fail(DV_ERR_HIP, "an earlier launch's in-kernel hand-over timed out (its results are invalid): %s (code 0x%x), workgroup %u, "
+                             "%u flag words missing; DVITS_GNX=0 plans no in-launch hand-over", what, code, wg, detail);
 }
 
 // internal (sampler): the time-embedding chain of n_evals evaluations (t_all [n_evals, B]) in one pass; returns 1 if this

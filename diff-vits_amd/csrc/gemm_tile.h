@@ -574,7 +574,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
       }
       DV_TRACE(22);
       DV_TRACE(4);
-      const bool gnx_h = p.gnx.xchg != nullptr;
+      const bool gnx_h = p.gnx.ho.words != nullptr;
       const int coff = kgrp * 16;                    // this wave's columns inside the fragment
       const int ncol = n0 + wn * 32 + coff;          // first of them
       const int rl = wm * 32 + l31, m = m0 + rl, mrow0 = m0 + wm * 32;
@@ -611,14 +611,14 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
       // other workgroups of the launch wait for the words, nobody waits for the stores; k_chain_ff has had this order since round 4
       const bool st_in = !padded || m_ok, st_pub = lane == 0 && mrow0 < p.M;   // (a zeroed row beyond M of an unpadded row space counts)
       const size_t st_e = (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol >> 4);
-      if (DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e);
+      if (DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<8, false>(p.stats16, p.gnx.ho.words, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e);
       if (m_in) {                                    // (padding rows are stored as zeros)
         const size_t ob = (size_t)m * p.ldo + ncol;
         if (p.out) store_row(p.out, ob + 4 * lh, vv);
         if (p.out_hi) store_planes8(p.out_hi, p.out_lo, ob, lh, vv);
       }
       DV_TRACE(17);
-      if (!DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e);
+      if (!DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<8, false>(p.stats16, p.gnx.ho.words, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e);
       DV_TRACE(18);
       if (gnx_h) {
         gnx_table(NWV);
@@ -725,7 +725,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 
   // ---- epilogue ----
   DV_TRACE(4);
-  const bool gnx = !SC1 && p.gnx.xchg != nullptr;
+  const bool gnx = !SC1 && p.gnx.ho.words != nullptr;
   // store 4 consecutive columns of one row: fp32 and/or split bf16 planes
   auto store4 = [&](size_t o, int nb, const float* v) {
     if (vec4) {
@@ -889,7 +889,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
       const int cb0 = (n0 + (wn * FN + j) * 32) >> 4;  // lanes 0 / 1 publish blocks cb0 / cb0 + 1
       const bool st_in = !padded || m_ok, st_pub = lane < 2 && mrow0 < p.M && (cb0 + lane) * 16 < p.N;
       const size_t st_e = (size_t)(mrow0 >> 5) * (p.N >> 4) + cb0 + lane;
-      unsigned long long* const st_x = gnx ? p.gnx.xchg : nullptr;
+      unsigned long long* const st_x = gnx ? p.gnx.ho.words : nullptr;
       if (DV_GNX_STATS_FIRST && p.stats16) gnx_block_stats<16, true>(p.stats16, st_x, vv, true, st_in, blk_cnt(mrow0), st_pub, st_e, lane);
       if (p.epi == EPI_STORE_NCT) {
         // [B, N, T_out]: the 32 lanes of a half-wave write 32 consecutive frames of one channel

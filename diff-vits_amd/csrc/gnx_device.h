@@ -16,6 +16,7 @@
 #pragma once
 #include "dv_common.h"
 #include "dv_device.h"
+#include "handover_device.h"
 
 struct GnxTile {
   int M, N;            // the producer's output [M, N]
@@ -159,13 +160,14 @@ __device__ __forceinline__ void gnx_finish_table(const GnxParams& gx, const GnxT
     const int g = gi < n1 ? g_lo + gi : g2_lo + (gi - n1);
     // poll the group's entries until none is EMPTY (all ones: the forward's first kernel resets the exchange words;
     // a published (sum, M2) is finite).  All tiles of the utterance are resident and arrive within the spread of the
-    // workgroups' k-loops; a lane re-reads only what it has not seen yet; bounded and flagged, never a hang
+    // workgroups' k-loops; a lane re-reads only what it has not seen yet; bounded and flagged, never a hang (handover_wait:
+    // the record names this launch's words, the workgroup and the group)
     constexpr int EPL = 4;                         // entries per lane: up to 256 per group (gemm_gnx_plan checks)
     unsigned long long w[EPL];
 #pragma unroll
     for (int k = 0; k < EPL; ++k) w[k] = ~0ull;
     const int ne = RB * nvb;
-    for (int spins = 0;; ++spins) {
+    handover_wait([&] {
       bool ok = true;
 #pragma unroll
       for (int k = 0; k < EPL; ++k) {
@@ -173,7 +175,7 @@ __device__ __forceinline__ void gnx_finish_table(const GnxParams& gx, const GnxT
         if (e < ne && w[k] == ~0ull) {
           const int rb = e / nvb, cb = g * nvb + (e - rb * nvb);     // 16-channel block of the concatenation
           if (cb < ncb)
-            w[k] = __hip_atomic_load(gx.xchg + (size_t)(bq * RB + rb) * ncb + cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            w[k] = __hip_atomic_load(gx.ho.words + (size_t)(bq * RB + rb) * ncb + cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           else {                                   // the skip's block: in memory since an earlier launch
             const float2 sv = reinterpret_cast<const float2*>(gx.sk_stat16)[(size_t)(bq * RB + rb) * ncs + (cb - ncb)];
             w[k] = gnx_word(sv.x, sv.y);
@@ -181,21 +183,8 @@ __device__ __forceinline__ void gnx_finish_table(const GnxParams& gx, const GnxT
           ok = ok && w[k] != ~0ull;
         }
       }
-      if (__all(ok)) break;
-      // (another launch has already given up: the run is lost and will be repeated on the fallback schedule - do not
-      // spend ~0.4 s per GEMM waiting for partners that a foreign kernel keeps off the CUs)
-      const bool lost = (spins & 63) == 63 && __hip_atomic_load(gx.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;
-      if (lost) break;
-      if (spins > gx.spin_max) {
-        if (lane == 0) {               // which GEMM, which workgroup, which group: reported by the next host call
-          gx.status[1] = (unsigned)(size_t)gx.xchg; gx.status[2] = blockIdx.x; gx.status[3] = (unsigned)g;
-          gx.status[4] = (unsigned)__builtin_popcountll(__ballot(!ok));
-          __hip_atomic_store(gx.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
+      return ok;
+    }, gx.ho.status, gx.ho.spin_max, gx.ho.words, (unsigned)g);
     double s1 = 0.0, q = 0.0;
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {

@@ -102,6 +102,11 @@ __device__ __forceinline__ void chain2_body(const P& p) {
   __shared__ __attribute__((aligned(256))) unsigned s_pf[64];
 
   // (every 64-byte line of the argument block is requested at once: see k_gemm)
+  static_assert(sizeof(ChainParams) == 408 &&
+                    dv_arg_lines(offsetof(ChainParams, M), offsetof(ChainParams, gamma), offsetof(ChainParams, w1_lo), offsetof(ChainParams, out1),
+                                 offsetof(ChainParams, u2), offsetof(ChainParams, xa_kf_hi), offsetof(ChainParams, xa_bias), offsetof(ChainParams, w3_lo),
+                                 offsetof(ChainParams, out3_lo), offsetof(ChainParams, sa_vf_lo), offsetof(ChainParams, nsplit)) == 0x3fu,
+                "the list below names lines 0-5 of ChainParams (the seventh holds the column-split launch's fields only)");
   asm volatile("" ::"s"(p.M), "s"(p.gamma), "s"(p.w1_lo), "s"(p.out1), "s"(p.u2), "s"(p.xa_kf_hi), "s"(p.xa_bias), "s"(p.w3_lo),
                "s"(p.out3_lo), "s"(p.sa_vf_lo), "s"(p.nsplit));
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1033,12 +1038,12 @@ __device__ __forceinline__ void chain_ff_stages(const ChainFFParams& p, char* co
       vv[4 * g] = acc[4 * g] + bv.x + rr.x; vv[4 * g + 1] = acc[4 * g + 1] + bv.y + rr.y;
       vv[4 * g + 2] = acc[4 * g + 2] + bv.z + rr.z; vv[4 * g + 3] = acc[4 * g + 3] + bv.w + rr.w;
     }
-    const bool gnx = p.gnx.xchg != nullptr;
+    const bool gnx = p.gnx.ho.words != nullptr;
     if (p.stats16) {
       // (padded row spaces: the utterance's last row block holds cnt < 32 frames that exist - the others stay out)
       const int Tv = p.Tv > 0 ? p.Tv : p.T, cnt = min(32, Tv - (m0 - (m0 / p.T) * p.T));
       const bool r_ok = l31 < cnt;                     // (the rows are NOT zeroed: both sums are masked, the raw rows stored)
-      gnx_block_stats<16, true>(p.stats16, p.gnx.xchg, vv, r_ok, r_ok, cnt, lane < 2, (size_t)blockIdx.x * (C / 16) + wn * 2 + lane, lane);
+      gnx_block_stats<16, true>(p.stats16, p.gnx.ho.words, vv, r_ok, r_ok, cnt, lane < 2, (size_t)blockIdx.x * (C / 16) + wn * 2 + lane, lane);
     }
     // (the statistics go out FIRST: the other row blocks of the utterance wait for them, nobody waits for these stores)
     if (p.out) store_row(p.out, (size_t)m * C + nf, vv);
@@ -1187,7 +1192,7 @@ bool chain_ff_supported(const ChainFFParams& p, int precision) {
 // gemm_gnx_plan, kernels_gemm.hip, for a launch whose tiles are whole rows)
 int chain_ff_gnx_plan(const ChainFFParams& p, int n_cu) {
   const GnxParams& gx = p.gnx;
-  if (!p.stats16 || gx.groups <= 0 || gx.groups > 64 || gx.sk_c < 0 || gx.sk_c > DV_GSK || gx.sk_c % 16 != 0 || gx.tscale) return 0;
+  if (!p.stats16 || gx.groups <= 0 || gx.groups > DV_GNX_MAX_GROUPS || gx.sk_c < 0 || gx.sk_c > DV_GSK || gx.sk_c % 16 != 0 || gx.tscale) return 0;
   if ((p.C + gx.sk_c) % gx.groups != 0) return 0;
   const int cpg = (p.C + gx.sk_c) / gx.groups;
   // (workgroup id = row block: an utterance's workgroups are consecutive ids - gemm_gnx_plan's launch-by-rounds rule)
@@ -1200,9 +1205,9 @@ static bool chain_ff_args_ok(const ChainFFParams& p, int precision, bool h3_glob
   if (!chain_ff_supported(p, precision)) return false;
   if (h3_global && (!p.a_hi || !p.a_lo || !p.rowstat)) return false;
   if (!p.wg_hi || !p.wg_lo || !p.bg || !p.ug || !p.wm_hi || !p.wm_lo || !p.bm || !p.res || (p.out_hi && !p.out_lo)) return false;
-  if (p.gnx.xchg) {
+  if (p.gnx.ho.words) {
     static const int n_cu = [] { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
-    if (!p.gnx.status || !p.gnx.y_hi || !p.gnx.y_lo || !p.gnx.gamma || !p.gnx.beta || chain_ff_gnx_plan(p, n_cu) <= 0) return false;
+    if (!p.gnx.ho.status || !p.gnx.y_hi || !p.gnx.y_lo || !p.gnx.gamma || !p.gnx.beta || chain_ff_gnx_plan(p, n_cu) <= 0) return false;
     if (p.gnx.sk_c > 0 && (!p.gnx.sk_x || !p.gnx.sk_stat16 || !p.gnx.sk_y_hi || !p.gnx.sk_y_lo)) return false;
   } else if (!p.out) return false;
   return true;

@@ -168,7 +168,7 @@ __device__ __forceinline__ void conv3_finish(const GemmParams& p, char* smem, co
   // ---- epilogue of the half fragment (the steps of gemm_tile.h's half-fragment epilogue) ----
   // Padded row space: a fragment beyond the tile's rows (the short last tile of an utterance) belongs to the NEXT utterance and is
   // not touched; rows [Tv_out, T_out) of this one are stored as zeros and kept out of the statistics (dv_common.h GemmParams).
-  const bool gnx_h = p.gnx.xchg != nullptr;
+  const bool gnx_h = p.gnx.ho.words != nullptr;
   const int coff = e_half * 16;                      // this wave's columns inside the fragment
   const int ncol = n0 + e_wn * 32 + coff;            // first of them
   const int m = m0 + e_wm * 32 + l31, mrow0 = m0 + e_wm * 32;
@@ -196,7 +196,7 @@ __device__ __forceinline__ void conv3_finish(const GemmParams& p, char* smem, co
   }
   DV_C3TRACE(5);
   if (p.stats16 && live)                             // this wave's 32 x 16 block statistics (gnx_device.h)
-    gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, !padded || m_ok, padded ? min(32, p.Tv_out - tfr) : 32, lane == 0,
+    gnx_block_stats<8, false>(p.stats16, p.gnx.ho.words, vv, true, !padded || m_ok, padded ? min(32, p.Tv_out - tfr) : 32, lane == 0,
                               (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol >> 4));
   DV_C3TRACE(6);
   if (gnx_h) {
@@ -223,8 +223,9 @@ __global__ __launch_bounds__(NT) void k_conv3(const GemmParams p) {
   __shared__ __attribute__((aligned(16))) float s_bias[BN];
   __shared__ GnxShared<BN> s_gnx;
   // (every 64-byte line of the argument block is requested at once: see k_gemm)
+  static_assert(sizeof(GemmParams) == 560 && DV_GEMM_ARG_LINES == 0x1ffu, "the list below must name every 64-byte line of GemmParams");
   asm volatile("" ::"s"(p.seg[0].a0_hi), "s"(p.seg[1].a0_hi), "s"(p.seg[1].pad), "s"(p.T_in), "s"(p.w_hi), "s"(p.M), "s"(p.res),
-               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.xchg), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn), "s"(p.wf_lo));
+               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.ho.words), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn), "s"(p.wf_lo));
   DV_C3TRACE(0);
   C3Tile tl;
   conv3_tile(p, tl, BM);
@@ -393,8 +394,9 @@ __global__ __launch_bounds__(NT) void k_conv3u(const GemmParams p) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   __shared__ __attribute__((aligned(16))) float s_bias[BN];
   __shared__ GnxShared<BN> s_gnx;
+  static_assert(sizeof(GemmParams) == 560 && DV_GEMM_ARG_LINES == 0x1ffu, "the list below must name every 64-byte line of GemmParams");
   asm volatile("" ::"s"(p.seg[0].a0_hi), "s"(p.seg[1].a0_hi), "s"(p.seg[1].pad), "s"(p.T_in), "s"(p.w_hi), "s"(p.M), "s"(p.res),
-               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.xchg), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn), "s"(p.wf_lo));
+               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.ho.words), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn), "s"(p.wf_lo));
   DV_C3TRACE(0);
   // tile: XCD x takes a band of row tiles (all their column tiles: an L2 fetches its rows of the source once); row tiles never span
   // two utterances (C3Tile: the last one of an utterance may be short)
@@ -559,7 +561,7 @@ __global__ __launch_bounds__(NT) void k_conv3u(const GemmParams p) {
   // ---- epilogue of the fragment: vv[4g + e] = column n0 + 32 e_wn + 8g + 4lh + e of row m0 + 32 e_wm + l31 ----
   // (padded row space: a fragment beyond the tile's rows belongs to the next utterance and is not touched; rows that do not exist
   // are stored as zeros and kept out of the statistics - conv3_finish)
-  const bool gnx_h = p.gnx.xchg != nullptr;
+  const bool gnx_h = p.gnx.ho.words != nullptr;
   const int ncol0 = n0 + e_wn * 32;
   const int m = m0 + e_wm * 32 + l31, mrow0 = m0 + e_wm * 32;
   const bool live = e_wm * 32 < tl.rows;             // (wave-uniform)
@@ -590,7 +592,7 @@ __global__ __launch_bounds__(NT) void k_conv3u(const GemmParams p) {
   }
   DV_C3TRACE(5);
   if (p.stats16 && live)                             // the fragment's two 32 x 16 block statistics (gnx_device.h)
-    gnx_block_stats<16, true>(p.stats16, p.gnx.xchg, vv, true, !padded || m_ok, padded ? min(32, p.Tv_out - tfr) : 32, lane < 2,
+    gnx_block_stats<16, true>(p.stats16, p.gnx.ho.words, vv, true, !padded || m_ok, padded ? min(32, p.Tv_out - tfr) : 32, lane < 2,
                               (size_t)(mrow0 >> 5) * (p.N >> 4) + (ncol0 >> 4) + lane, lane);
   DV_C3TRACE(6);
   if (gnx_h) {
@@ -651,8 +653,9 @@ __global__ __launch_bounds__(NT_S) void k_conv3s(const GemmParams p) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   __shared__ __attribute__((aligned(16))) float s_bias[BN];
   __shared__ GnxShared<BN> s_gnx;
+  static_assert(sizeof(GemmParams) == 560 && DV_GEMM_ARG_LINES == 0x1ffu, "the list below must name every 64-byte line of GemmParams");
   asm volatile("" ::"s"(p.seg[0].a0_hi), "s"(p.seg[1].a0_hi), "s"(p.seg[1].pad), "s"(p.T_in), "s"(p.w_hi), "s"(p.M), "s"(p.res),
-               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.xchg), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn), "s"(p.wf_lo));
+               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.ho.words), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn), "s"(p.wf_lo));
   const GemmSeg& sg = p.seg[0];
   const GemmSeg& sh = p.seg[1];
   const int c0 = sg.c0, c1 = sg.c1, CIN = c0 + c1;

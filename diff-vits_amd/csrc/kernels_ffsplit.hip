@@ -90,7 +90,14 @@ __global__ __launch_bounds__(NT) void k_ff_split(const FFSplitParams p) {
   __shared__ GnxShared<64> s_gnx;
   __shared__ __attribute__((aligned(256))) unsigned s_pf[64];
   // (every 64-byte line of the argument block is requested at once: see k_gemm)
-  asm volatile("" ::"s"(p.M), "s"(p.rowstat), "s"(p.wg_lo), "s"(p.wm_hi), "s"(p.res), "s"(p.out_lo), "s"(p.flags), "s"(p.gnx.xchg),
+  // (lines 0-2, 4 and 5 of FFSplitParams' six: line 3 holds GroupNorm fields that only gnx_finish_table reads)
+  static_assert(sizeof(FFSplitParams) == 328 &&
+                    dv_arg_lines(offsetof(FFSplitParams, M), offsetof(FFSplitParams, rowstat), offsetof(FFSplitParams, wg_lo), offsetof(FFSplitParams, wm_hi),
+                                 offsetof(FFSplitParams, res), offsetof(FFSplitParams, out_lo), offsetof(FFSplitParams, ho.words),
+                                 offsetof(FFSplitParams, gnx.ho.words), offsetof(FFSplitParams, gnx.y_hi), offsetof(FFSplitParams, gnx.sk_x),
+                                 offsetof(FFSplitParams, gnx.sk_raw_lo)) == 0x37u,
+                "the list below names these lines of FFSplitParams: look at it again when the layout changes");
+  asm volatile("" ::"s"(p.M), "s"(p.rowstat), "s"(p.wg_lo), "s"(p.wm_hi), "s"(p.res), "s"(p.out_lo), "s"(p.ho.words), "s"(p.gnx.ho.words),
                "s"(p.gnx.y_hi), "s"(p.gnx.sk_x), "s"(p.gnx.sk_raw_lo));
   DV_FTRACE(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -430,7 +437,7 @@ __global__ __launch_bounds__(NT) void k_ff_split(const FFSplitParams p) {
   // one flag word per WAVE: a finishing wave needs the partial sums of exactly one wave of every workgroup of its row block (the one
   // that multiplied its column fragment) - it waits for those four / eight words, not for whole workgroups, and no barrier sits
   // between a wave's last store and its flag [v3: one flag per workgroup behind a __syncthreads]
-  if (lane == 0) __hip_atomic_store(p.flags + ((size_t)rb * NSPL + s) * NWV + wave, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (lane == 0) __hip_atomic_store(p.ho.words + ((size_t)rb * NSPL + s) * NWV + wave, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   DV_FTRACE(7);
   const int b_item = m0 / p.T, Tv = p.Tv > 0 ? p.Tv : p.T;
   const int t_row = f_m - b_item * p.T;
@@ -444,22 +451,9 @@ __global__ __launch_bounds__(NT) void k_ff_split(const FFSplitParams p) {
       // (the wave of workgroup `lane` that wrote this unit's block: column fragment f_hf / 2 - and, with two k-groups, the group
       // that owns the item (fragment, row fragment))
       const int cfw = f_hf >> 1, ww = G::KGB == 1 ? cfw : ((((cfw % G::NFW) * RF + f_rf) & 1) * 4 + cfw / G::NFW);
-      const unsigned long long* fl = p.flags + (size_t)rb * NSPL * NWV + ww;
-      for (int spins = 0;; ++spins) {
-        bool ok = true;
-        if (lane < NSPL) ok = __hip_atomic_load(fl + lane * NWV, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != ~0ull;
-        if (__all(ok)) break;
-        const bool lost = (spins & 63) == 63 && __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;
-        if (lost) break;
-        if (spins > p.spin_max) {
-          if (lane == 0) {
-            p.status[1] = (unsigned)(size_t)p.flags; p.status[2] = blockIdx.x; p.status[3] = 0xff5u; p.status[4] = (unsigned)__builtin_popcountll(__ballot(!ok));
-            __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          }
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
+      const unsigned long long* fl = p.ho.words + (size_t)rb * NSPL * NWV + ww;
+      handover_wait([&] { return lane >= NSPL || __hip_atomic_load(fl + lane * NWV, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != ~0ull; },
+                    p.ho.status, p.ho.spin_max, p.ho.words, HO_FF_PARTIAL);
       asm volatile("" ::: "memory");
     }
     DV_FTRACE(8);
@@ -490,7 +484,7 @@ __global__ __launch_bounds__(NT) void k_ff_split(const FFSplitParams p) {
     DV_FTRACE(9);
     if (p.stats16) {   // this unit's 32 x 16 block: (sum, squared deviations about its own mean) over the frames that exist
       const int cnt = min(32, Tv - (m0 + f_rf * 32 - b_item * p.T));
-      gnx_block_stats<8, false>(p.stats16, p.gnx.xchg, vv, true, m_ok, cnt, lane == 0, (size_t)((m0 >> 5) + f_rf) * (C >> 4) + f_hf);
+      gnx_block_stats<8, false>(p.stats16, p.gnx.ho.words, vv, true, m_ok, cnt, lane == 0, (size_t)((m0 >> 5) + f_rf) * (C >> 4) + f_hf);
     }
     // (the statistics go out FIRST: other workgroups wait for them, nobody waits for these stores)
     const size_t ob = (size_t)f_m * C + f_hf * 16;
@@ -498,7 +492,7 @@ __global__ __launch_bounds__(NT) void k_ff_split(const FFSplitParams p) {
     if (p.out_hi) store_planes8(p.out_hi, p.out_lo, ob, lh, vv);
   }
   DV_FTRACE(10);
-  if (p.gnx.xchg) {
+  if (p.gnx.ho.words) {
     // ---- the consumer's GroupNorm (+ SiLU) of this block's output, a concatenated skip tensor included (gnx_device.h): the
     //      workgroup's finishing tile [64 rows x C / nspl columns] is treated exactly like a GEMM tile ----
     GnxTile t;
@@ -558,7 +552,7 @@ size_t ff_split_xbuf_floats(int M, int C, int nspl, int rows) {
 // (the conditions of gemm_gnx_plan, kernels_gemm.hip)
 int ff_split_gnx_plan(const FFSplitParams& p, int n_cu) {
   const GnxParams& gx = p.gnx;
-  if (!p.stats16 || gx.groups <= 0 || gx.groups > 64 || gx.sk_c < 0 || gx.sk_c % 16 != 0 || gx.tscale) return 0;
+  if (!p.stats16 || gx.groups <= 0 || gx.groups > DV_GNX_MAX_GROUPS || gx.sk_c < 0 || gx.sk_c % 16 != 0 || gx.tscale) return 0;
   if ((p.C + gx.sk_c) % gx.groups != 0) return 0;
   const int cpg = (p.C + gx.sk_c) / gx.groups;
   // (workgroup id = row block * nspl + slice, plain order: an utterance's workgroups are consecutive ids, spread evenly over the
@@ -572,14 +566,14 @@ int ff_split_gnx_plan(const FFSplitParams& p, int n_cu) {
 hipError_t launch_ff_split(const FFSplitParams& p, int precision, hipStream_t st) {
   if (!ff_split_supported(p, precision)) return hipErrorInvalidValue;
   if (!p.a_hi || !p.a_lo || !p.rowstat || !p.wg_hi || !p.wg_lo || !p.bg || !p.ug || !p.wm_hi || !p.wm_lo || !p.bm || !p.res || !p.xbuf ||
-      !p.flags || !p.status || (p.out_hi && !p.out_lo))
+      !p.ho.words || !p.ho.status || (p.out_hi && !p.out_lo))
     return hipErrorInvalidValue;
   static const int n_cu = [] { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
   // (the partial-sum hand-over waits for the nspl <= 8 workgroups of its own row block - consecutive ids; kernels_gemm.hip
   // gemm_handover_rounds - else every workgroup of the launch resident at once)
   if (!gemm_handover_rounds() && (p.M / p.rows) * p.nspl > n_cu) return hipErrorInvalidValue;
-  if (p.gnx.xchg) {
-    if (!p.gnx.status || !p.gnx.y_hi || !p.gnx.y_lo || !p.gnx.gamma || !p.gnx.beta || ff_split_gnx_plan(p, n_cu) <= 0) return hipErrorInvalidValue;
+  if (p.gnx.ho.words) {
+    if (!p.gnx.ho.status || !p.gnx.y_hi || !p.gnx.y_lo || !p.gnx.gamma || !p.gnx.beta || ff_split_gnx_plan(p, n_cu) <= 0) return hipErrorInvalidValue;
     if (p.gnx.sk_c > 0 && (!p.gnx.sk_x || !p.gnx.sk_stat16 || !p.gnx.sk_y_hi || !p.gnx.sk_y_lo)) return hipErrorInvalidValue;
   } else if (!p.out) return hipErrorInvalidValue;
   if (p.C == 256) return p.rows == 64 ? ffs_launch_one<256, 4, 2>(p, st) : ffs_launch_one<256, 4, 1>(p, st);

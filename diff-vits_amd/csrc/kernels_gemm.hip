@@ -34,8 +34,9 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void k_gemm(const GemmParams p) 
   // every 64-byte line of the argument block is requested NOW, together: the tile mapping below branches on a field of
   // the last line, and the loads of the tile routine would otherwise only be issued once that branch has resolved (two
   // dependent scalar-cache misses at the head of every workgroup: measured +300 cycles)
+  static_assert(sizeof(GemmParams) == 560 && DV_GEMM_ARG_LINES == 0x1ffu, "the list below must name every 64-byte line of GemmParams");
   asm volatile("" ::"s"(p.seg[0].a0_hi), "s"(p.seg[1].a0_hi), "s"(p.seg[1].pad), "s"(p.T_in), "s"(p.w_hi), "s"(p.M), "s"(p.res),
-               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.xchg), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn));
+               "s"(p.out_hi), "s"(p.zero_page), "s"(p.ln_u), "s"(p.gnx.ho.words), "s"(p.gnx.y_hi), "s"(p.xcd_n), "s"(p.xcd_inv_tn));
   // ONE call site of the tile routine.  [Rounds 1-3 called it from both branches of the mapping: two inlined copies.  Waves
   // leave the routine at different points (k-groups that hand their sums over), so the structurised control flow runs from the
   // first copy's epilogue THROUGH the second copy under an empty exec mask - and hipcc's wait-count insertion, which knows
@@ -342,7 +343,7 @@ bool gemm_handover_rounds() {
 int gemm_gnx_plan(const GemmParams& p, int n_cu) {
   if (p.force_tile != GT_AUTO || (p.epi != EPI_STORE && p.epi != EPI_RESIDUAL) || !p.stats16 || p.rowmask || p.relu) return 0;
   const int skc = p.gnx.sk_c;                          // concatenated consumer: groups of [output | skip]
-  if (p.M != p.B * p.T_out || p.gnx.groups <= 0 || p.gnx.groups > 64 || skc < 0 || (p.N + skc) % p.gnx.groups != 0) return 0;
+  if (p.M != p.B * p.T_out || p.gnx.groups <= 0 || p.gnx.groups > DV_GNX_MAX_GROUPS || skc < 0 || (p.N + skc) % p.gnx.groups != 0) return 0;
   const int cpg = (p.N + skc) / p.gnx.groups;
   if (cpg % 16 != 0 || p.N % 16 != 0 || skc % 16 != 0) return 0;
   int bm, bn, tu;
@@ -391,7 +392,7 @@ hipError_t launch_gemm(const GemmParams& pin, int precision, hipStream_t st) {
       for (int s2 = 0; s2 < p.nseg; ++s2) k += p.seg[s2].taps * (p.seg[s2].c0 + p.seg[s2].c1);
       snprintf(g_trace_desc, sizeof(g_trace_desc), "M=%d N=%d K=%d taps=%d nseg=%d epi=%d stride=%d up=%d%s%s%s%s%s%s split=%d%s",
                p.M, p.N, k, p.seg[0].taps, p.nseg, p.epi, p.stride, p.up_mode, p.stats ? " +colstats" : "", p.stats16 ? " +stats16" : "",
-               p.gnx.xchg ? " +gnx" : "", p.out_hi ? " +planes" : "", p.rowstat_out ? " +rowstat" : "", p.ln_stat ? " +ln" : "",
+               p.gnx.ho.words ? " +gnx" : "", p.out_hi ? " +planes" : "", p.rowstat_out ? " +rowstat" : "", p.ln_stat ? " +ln" : "",
                p.sk_buf ? p.sk_split : 0, (p.sk_buf && p.sk_ticket && p.sk_split == 2) ? "f" : "");
     }
     ++g_trace_no;
@@ -402,7 +403,7 @@ hipError_t launch_gemm(const GemmParams& pin, int precision, hipStream_t st) {
   // padded row spaces (GemmParams): 0 = no padding
   if (p.Tv_out <= 0) p.Tv_out = p.T_out;
   if (p.Tv_in <= 0) p.Tv_in = p.T_in;
-  if (p.Tv_out > p.T_out || p.Tv_in > p.T_in || ((p.stats16 || p.gnx.xchg) && p.Tv_out <= p.T_out - 32)) return hipErrorInvalidValue;
+  if (p.Tv_out > p.T_out || p.Tv_in > p.T_in || ((p.stats16 || p.gnx.ho.words) && p.Tv_out <= p.T_out - 32)) return hipErrorInvalidValue;
   if (p.T_out < 1 || (unsigned long long)(p.M > 0 ? p.M : 1) * (unsigned long long)p.T_out >= (1ull << 32)) return hipErrorInvalidValue;
   p.tout_magic = gemm_tout_magic(p.T_out);
   if (p.ln_stat && (p.ln_nblk < 1 || p.ln_nblk > 16)) return hipErrorInvalidValue;   // (a row's LayerNorm partials are held in registers: gemm_tile.h)
@@ -414,9 +415,9 @@ hipError_t launch_gemm(const GemmParams& pin, int precision, hipStream_t st) {
     if (gemm_conv3_shape_ok(p) && p.Kp == gemm_conv3_k(p)) p.c3_route = 1;
     else if (gemm_conv3_up_ok(p) && p.Kp == 3 * (p.seg[0].c0 + p.seg[0].c1)) p.c3_route = 2;
   }
-  if (p.gnx.xchg && p.sk_mode == 0) {            // (checked once, before the split-K recursion)
+  if (p.gnx.ho.words && p.sk_mode == 0) {            // (checked once, before the split-K recursion)
     static const int n_cu = [] { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
-    if (!p.gnx.status || !p.gnx.y_hi || !p.gnx.gamma || !p.gnx.beta || gemm_gnx_plan(p, n_cu) <= 0) return hipErrorInvalidValue;
+    if (!p.gnx.ho.status || !p.gnx.y_hi || !p.gnx.gamma || !p.gnx.beta || gemm_gnx_plan(p, n_cu) <= 0) return hipErrorInvalidValue;
     if (p.gnx.sk_c > 0 && (!p.gnx.sk_x || !p.gnx.sk_stat16 || !p.gnx.sk_y_hi || (x3 && !p.gnx.sk_y_lo) || p.gnx.tscale)) return hipErrorInvalidValue;
   }
   if (p.sk_buf && p.sk_split == 2 && p.sk_ticket && p.sk_mode == 0) {

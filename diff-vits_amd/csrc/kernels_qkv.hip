@@ -36,6 +36,7 @@
 // jobs are (head, row fragment) pairs of 64-row blocks with d <= 32).  The C <= 384 instantiations compute what they computed.
 #include "dv_common.h"
 #include "dv_device.h"
+#include "handover_device.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -104,7 +105,13 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   __shared__ __attribute__((aligned(16))) float s_gscale[C], s_gshift[C];
   __shared__ __attribute__((aligned(16))) float2 s_ln[G::RB];   // per row (mean, rstd) of h
   // (every 64-byte line of the argument block is requested at once: see k_gemm)
-  asm volatile("" ::"s"(p.M), "s"(p.gamma), "s"(p.w1_lo), "s"(p.out1), "s"(p.u2), "s"(p.sa_kf_hi), "s"(p.sa_vf_lo), "s"(p.qs_flags));
+  // (lines 0-2, 4 and 5 of ChainParams' seven: line 3 holds the cross-attention fields, line 6 qs_o_* and qs_xcd)
+  static_assert(sizeof(ChainParams) == 408 &&
+                    dv_arg_lines(offsetof(ChainParams, M), offsetof(ChainParams, gamma), offsetof(ChainParams, w1_lo), offsetof(ChainParams, out1),
+                                 offsetof(ChainParams, u2), offsetof(ChainParams, sa_kf_hi), offsetof(ChainParams, sa_vf_lo),
+                                 offsetof(ChainParams, ho.words)) == 0x37u,
+                "the list below names these lines of ChainParams: look at it again when the layout changes");
+  asm volatile("" ::"s"(p.M), "s"(p.gamma), "s"(p.w1_lo), "s"(p.out1), "s"(p.u2), "s"(p.sa_kf_hi), "s"(p.sa_vf_lo), "s"(p.ho.words));
   DV_QTRACE(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
@@ -363,8 +370,8 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
   __syncthreads();
   if (tid == 0) {
     const unsigned long long fv = 1ull + xcc;        // (the flag says where it was written)
-    if (xl) *reinterpret_cast<volatile unsigned long long*>(p.qs_flags + (size_t)rb * G::NSPL + s) = fv;
-    else __hip_atomic_store(p.qs_flags + (size_t)rb * G::NSPL + s, fv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (xl) *reinterpret_cast<volatile unsigned long long*>(p.ho.words + (size_t)rb * G::NSPL + s) = fv;
+    else __hip_atomic_store(p.ho.words + (size_t)rb * G::NSPL + s, fv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // stage 2's first weight fragments fly during the hand-over (MODE 0: of the merged q | k | v loop below)
   const int nfq = s * 2 + cf, nfk = C / 32 + s * 2 + cf, nfv = 2 * (C / 32) + s * 2 + cf;
@@ -391,39 +398,21 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
 
   // ================= all-gather of h: wait for the row block's flags (every wave polls for itself), rows back as fp32 =================
   auto wait_flags = [&](const unsigned long long* fl, unsigned code) __attribute__((always_inline)) {
-    for (int spins = 0;; ++spins) {
-      bool ok = true;
-      unsigned long long fv = 0;
-      if (lane < G::NSPL) {
-        if (xl) asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(fv) : "v"(fl + lane) : "memory");
-        else fv = __hip_atomic_load(fl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        ok = fv != ~0ull;
-      }
-      if (__all(ok)) {
-        // XCD-local hand-over: every partner must have run on THIS XCD (its stores sit in this L2).  A placement other than
-        // "workgroup b on XCD b % 8" is reported like a timed-out wait: the run is repeated on the fallback schedule
-        if (xl && __any(lane < G::NSPL && fv != 1ull + xcc)) {
-          if (lane == 0) {
-            p.qs_status[1] = (unsigned)(size_t)p.qs_flags; p.qs_status[2] = blockIdx.x; p.qs_status[3] = 0xc2u; p.qs_status[4] = xcc;
-            __hip_atomic_store(p.qs_status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          }
-        }
-        break;
-      }
-      const bool lost = (spins & 63) == 63 && __hip_atomic_load(p.qs_status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;
-      if (lost) break;
-      if (spins > p.qs_spin) {
-        if (lane == 0) {
-          p.qs_status[1] = (unsigned)(size_t)p.qs_flags; p.qs_status[2] = blockIdx.x; p.qs_status[3] = code; p.qs_status[4] = (unsigned)__builtin_popcountll(__ballot(!ok));
-          __hip_atomic_store(p.qs_status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
+    unsigned long long fv = 0;                       // this lane's flag as last read
+    const bool got = handover_wait([&] {
+      if (lane >= G::NSPL) return true;
+      if (xl) asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(fv) : "v"(fl + lane) : "memory");
+      else fv = __hip_atomic_load(fl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return fv != ~0ull;
+    }, p.ho.status, p.ho.spin_max, p.ho.words, code);
+    // XCD-local hand-over: every partner must have run on THIS XCD (its stores sit in this L2).  A placement other than
+    // "workgroup b on XCD b % 8" is reported like a timed-out wait: the run is repeated on the fallback schedule
+    if (got && xl && __any(lane < G::NSPL && fv != 1ull + xcc)) {
+      if (lane == 0) handover_report(p.ho.status, p.ho.words, HO_QKV_XCD, xcc);
     }
     asm volatile("" ::: "memory");
   };
-  wait_flags(p.qs_flags + (size_t)rb * G::NSPL, 0xc1u);
+  wait_flags(p.ho.words + (size_t)rb * G::NSPL, HO_QKV_H);
   DV_QTRACE(5);
   {
     const float4* hr = reinterpret_cast<const float4*>(p.out1 + (size_t)(m0 + r_row) * C + 4 * r_e8);
@@ -672,11 +661,11 @@ __global__ __launch_bounds__(NT) void k_qkv_split(const ChainParams p) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    const unsigned long long* fl2 = p.qs_flags + (size_t)(p.M / BM) * G::NSPL + (size_t)rb * G::NSPL;
+    const unsigned long long* fl2 = p.ho.words + (size_t)(p.M / BM) * G::NSPL + (size_t)rb * G::NSPL;
     if (tid == 0) *reinterpret_cast<volatile unsigned long long*>(const_cast<unsigned long long*>(fl2) + s) = 1ull + xcc;
     // stage-3 vectors of this lane's finished columns
     const float4 b3v = *reinterpret_cast<const float4*>(p.b3 + ncol);
-    wait_flags(fl2, 0xc3u);
+    wait_flags(fl2, HO_QKV_O);
     {
       // the row block's attention output (all heads) -> the row region, by L1-bypassing LDS-DMA (served by the XCD's L2)
       const unsigned a_base = (unsigned)(size_t)a_reg;
@@ -904,7 +893,7 @@ int qkv_split_flags(const ChainParams& p) { return (p.M / qrows(p.C)) * (p.C / B
 hipError_t launch_qkv_split(const ChainParams& p, int precision, hipStream_t st) {
   if (!qkv_split_supported(p, precision)) return hipErrorInvalidValue;
   if ((p.amode == 1 && (!p.x || !p.stat16 || !p.gamma || !p.beta)) || !p.w1_hi || !p.w1_lo || !p.b1 || !p.w2_hi || !p.w2_lo || !p.b2 || !p.u2 ||
-      !p.qs_flags || !p.qs_status)
+      !p.ho.words || !p.ho.status)
     return hipErrorInvalidValue;
   if (!gemm_handover_rounds()) {                     // (else: the wait is for C / 64 consecutive workgroup ids)
     static const int n_cu = [] { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n; }();
