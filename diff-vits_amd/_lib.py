@@ -167,6 +167,9 @@ SIGNATURES = {
     "dv_op_layer_norm": (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
     "dv_op_layer_norm_into": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_float] + [C.c_int32] * 3 + [C.c_void_p]),
     "dv_op_prompt_pre": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),
+    "dv_op_timestep_embedding": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "dv_op_small_linear": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 8 + [C.c_void_p]),
+    "dv_op_pool_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_linear_ln": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 5 + [C.c_void_p] * 4),
     "dv_op_linear_gn": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_float, C.c_int32] + [C.c_void_p] * 5),
 }

@@ -3159,6 +3159,64 @@ extern "C" int dv_op_prompt_pre(const float* prompt, const float* keep, const fl
   return DV_OK;
 }
 
+// ----------------------------------------------------------------------------- conditioning entry points
+// The fp32 kernels of the conditioning path (kernels_misc.hip) through the launchers the cond and step schedules call.
+
+extern "C" int dv_op_timestep_embedding(const float* t, float* out, int32_t B, int32_t dim, void* stream) {
+  if (!t || !out) return dv_fail(DV_ERR_INVALID, "dv_op_timestep_embedding: null pointer");
+  if (B < 1 || dim < 2 || dim % 2 != 0 || (int64_t)B * (dim / 2) > INT32_MAX - 256)
+    return dv_fail(DV_ERR_INVALID, "dv_op_timestep_embedding: B = %d >= 1 rows of an even dim = %d >= 2, B * dim / 2 < 2^31 - 256, are required", B, dim);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_timestep_sincos(t, out, B, dim, st);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_timestep_embedding: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
+extern "C" int dv_op_small_linear(const float* in, int32_t ldin, const float* w, const float* bias, const float* add, float* out, int32_t ldo,
+                                  int32_t M, int32_t K, int32_t N, int32_t silu_in, int32_t silu_out, int32_t route, int32_t add_rows,
+                                  void* stream) {
+  if (!in || !w || !out) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: null pointer");
+  if (route != 0 && route != 1) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: route %d is neither 0 (k_small_linear) nor 1 (k_small_linear_t)", route);
+  if ((silu_in != 0 && silu_in != 1) || (silu_out != 0 && silu_out != 1)) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: silu_in and silu_out are 0 or 1");
+  if (M < 1 || M > 65536 || K < 1 || K > 16384 || N < 1 || N > (1 << 20))
+    return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: 1 <= M = %d <= 65536, 1 <= K = %d <= 16384, 1 <= N = %d <= 2^20 are required", M, K, N);
+  if (ldin < K || ldo < N) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: ldin = %d >= K = %d and ldo = %d >= N = %d are required", ldin, K, ldo, N);
+  if (add_rows < 0 || (add_rows > 0 && (route != 1 || !add)))
+    return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: add_rows = %d needs route 1 and an add tensor", add_rows);
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = route == 0 ? launch_small_linear(in, ldin, w, bias, add, out, ldo, M, K, N, silu_in, silu_out, st)
+                                  : launch_small_linear_t(in, ldin, w, bias, add, out, ldo, M, K, N, silu_in, silu_out, st, add_rows);
+  if (e == hipErrorInvalidValue)   // the launchers' own refusals: nothing was launched
+    return route == 0 ? dv_fail(DV_ERR_INVALID, "dv_op_small_linear: M x K = %d x %d floats exceed the 64 KiB of LDS k_small_linear stages its rows in", M, K)
+                      : dv_fail(DV_ERR_INVALID, "dv_op_small_linear: K = %d exceeds the 512 input columns k_small_linear_t's 64 KiB of LDS hold", K);
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_small_linear: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
+extern "C" int dv_op_pool_attention(float* seq, const float* pos, const float* q, const float* kv, float* out, int32_t B, int32_t L, int32_t D,
+                                    int32_t heads, int32_t stage, void* stream) {
+  if (stage != 0 && stage != 1) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: stage %d is neither 0 (k_mean_token) nor 1 (k_pool_attn)", stage);
+  if (B < 1 || B > 65535 || L < 1 || L > (1 << 20) || D < 1 || D > 8192)
+    return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: 1 <= B = %d <= 65535, 1 <= L = %d <= 2^20, 1 <= D = %d <= 8192 are required", B, L, D);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e;
+  if (stage == 0) {
+    if (!seq || !pos || q || kv || out) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: stage 0 takes seq and pos only");
+    e = launch_mean_token(seq, pos, B, L, D, st);
+  } else {
+    if (!q || !kv || !out || seq || pos) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: stage 1 takes q, kv and out only");
+    if (heads < 1 || heads > 65535 || D % heads != 0) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: D = %d is not a multiple of heads = %d >= 1", D, heads);
+    e = launch_pool_attn(q, kv, out, B, L + 1, D, heads, st);
+    if (e == hipErrorInvalidValue)   // the launcher's own refusal: nothing was launched
+      return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: D / heads = %d exceeds the 8 channels per head k_pool_attn accumulates", D / heads);
+  }
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_pool_attention: launch failed: %s", hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
 // Producer GEMM (+ residual) with the raw planes and the row partials of ln_produce, then the consumer GEMM as ln_consume sets it
 // up: gamma folded into the packed weights, u and the beta-folded bias by the packing launchers Builder::pack runs.
 extern "C" int dv_op_linear_ln(const float* x, const float* w1, const float* b1, const float* res, const float* gamma, const float* beta,

@@ -735,6 +735,27 @@ int dv_op_linear_gn(const float* x, const float* w, const float* b, const float*
                     int32_t Tp, int32_t K, int32_t C, int32_t G, float eps, int32_t route, float* y, float* stats,
                     uint16_t* y_norm_hi, uint16_t* y_norm_lo, void* stream);
 
+/* ---- the conditioning path's fp32 kernels in isolation (csrc/kernels_misc.hip), each through the launcher the cond and step
+ * schedules call.  Device pointers; every argument is checked before anything is launched (DV_ERR_INVALID), the call returns
+ * after the stream has drained. ---- */
+/* k_timestep_sincos: t [B] -> out [B, dim] = [cos(t f_j) | sin(t f_j)], f_j = exp(-ln(10000) j / (dim / 2)); dim even. */
+int dv_op_timestep_embedding(const float* t, float* out, int32_t B, int32_t dim, void* stream);
+/* out [M, N] (row pitch ldo) = act_out(act_in(in [M, K], row pitch ldin) w^T + bias [N]) + add [., N] (row pitch ldo); act = SiLU
+ * where silu_in / silu_out is 1; bias and add may be NULL.
+ *   route 0  k_small_linear, w [N, K]: one wave per output column; M * K floats must fit 64 KiB of LDS.
+ *   route 1  k_small_linear_t, w [K, N] (already transposed): lane per output column, eight k-eighths; K <= 512.  M <= 8 and
+ *            9 <= M <= 16 run one chunk of 8 / 16 rows, M > 16 chunks of 8 rows.  add_rows > 0: row r adds add[r % add_rows].
+ * A size a launcher refuses is DV_ERR_INVALID with nothing launched. */
+int dv_op_small_linear(const float* in, int32_t ldin, const float* w, const float* bias, const float* add, float* out, int32_t ldo,
+                       int32_t M, int32_t K, int32_t N, int32_t silu_in, int32_t silu_out, int32_t route, int32_t add_rows,
+                       void* stream);
+/* The attention pooling of the text states, S = L + 1 rows per utterance.
+ *   stage 0  k_mean_token, in place on seq [B, L + 1, D]: row 0 = mean of rows 1..L + pos [D]; seq and pos only.
+ *   stage 1  k_pool_attn: q [B, D], kv [B (L + 1), 2 D] (keys | values) -> out [B, D], `heads` heads of D / heads <= 8 channels,
+ *            q and k each scaled by (D / heads)^-1/4; q, kv and out only. */
+int dv_op_pool_attention(float* seq, const float* pos, const float* q, const float* kv, float* out, int32_t B, int32_t L, int32_t D,
+                         int32_t heads, int32_t stage, void* stream);
+
 /* ---- vocoder: Vocos backbone + ISTFT head (csrc/voc.hip, csrc/kernels_voc.hip) --------
  * mel [B, n_mels, T] (the denormalised log-mel) -> wave [B, (T - 1) * hop] float32 and samples [B] int64.  Ragged batches: with
  * lengths [B] (int64, device) every row is its own utterance of L_b frames - filter taps read zeros at t < 0 and t >= L_b, the
