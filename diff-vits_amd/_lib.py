@@ -159,6 +159,8 @@ SIGNATURES = {
     "dv_op_linear_planes": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 6 + [C.c_void_p]),
     "dv_op_gemm": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 11 + [C.c_void_p]),
     "dv_op_gemm_variant": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_int32)] * 3),
+    "dv_op_conv_rows": (C.c_int, [C.c_void_p] * 10 + [C.c_int32] * 14 + [C.c_void_p]),
+    "dv_op_conv_rows_variant": (C.c_int, [C.c_int32] * 14 + [C.POINTER(C.c_int32)] * 4 + [C.c_int32]),
     "dv_op_group_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),
     "dv_op_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p]),
     "dv_op_attention_prec": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p]),
@@ -181,6 +183,7 @@ GT = {"auto": 0, "T0": 1, "T1": 2, "T2": 3, "T2S": 4, "T2G": 5, "T3": 6, "T4": 7
 GT_BK64 = 0x100
 GEMM_STORE, GEMM_RESIDUAL, GEMM_GEGLU = 0, 1, 2
 GEMM_SPLITK_FUSED = 0x100
+UP_NONE, UP_X2, UP_SIZE = 0, 1, 2     # DV_UP_* of dv_op_conv_rows
 
 _lib = None
 

@@ -2962,6 +2962,117 @@ extern "C" int dv_op_gemm(const float* x, const float* w, const float* bias, con
   return DV_OK;
 }
 
+// ---- dv_op_conv_rows: k_gemm's convolution operand path (gemm_tile.h prep_a / advance / utt_of) as Builder::resample and the resnet
+// fallback launch it: channels-last sources in a padded row space, taps, stride 2, nearest upsampling, [a0 | a1], a second k-segment ----
+static_assert(DV_UP_NONE == UP_NONE && DV_UP_X2 == UP_X2 && DV_UP_SIZE == UP_SIZE, "public upsampling modes");
+constexpr int CONV_ROWS_GUARD = 32;   // rows of NaN behind every operand plane the kernel reads
+
+// Checks the shape and fills the host-only fields of g (no pointers, nothing launched).  0, or DV_ERR_INVALID with the message set.
+static int conv_rows_shape(GemmParams& g, int B, int T, int Tp_in, int c0, int c1, int c_sc, int Cout, int taps, int stride, int up_mode,
+                           int up_T, int Tp_out, int with_stats, int tile, int precision, const char* what) {
+  if (B <= 0 || T <= 0 || Tp_in < T || Tp_in > 32768 || c0 <= 0 || c1 < 0 || c_sc < 0 || Cout <= 0 || Tp_out <= 0 || Tp_out > 32768)
+    return dv_fail(DV_ERR_INVALID, "%s: B = %d, T = %d, Tp_in = %d, c0 = %d, c1 = %d, c_sc = %d, Cout = %d, Tp_out = %d: positive sizes, T <= Tp_in <= 32768", what, B, T, Tp_in, c0, c1, c_sc, Cout, Tp_out);
+  if (taps != 1 && taps != 3) return dv_fail(DV_ERR_INVALID, "%s: taps = %d is not 1 or 3", what, taps);
+  if (stride != 1 && stride != 2) return dv_fail(DV_ERR_INVALID, "%s: stride = %d is not 1 or 2", what, stride);
+  if (up_mode != DV_UP_NONE && up_mode != DV_UP_X2 && up_mode != DV_UP_SIZE) return dv_fail(DV_ERR_INVALID, "%s: up_mode %d is not a DV_UP_*", what, up_mode);
+  if (up_mode == DV_UP_SIZE ? (up_T <= 0 || up_T > 32768) : up_T != 0) return dv_fail(DV_ERR_INVALID, "%s: up_T = %d goes with DV_UP_SIZE (1 .. 32768 frames), and only with it", what, up_T);
+  if (up_mode != DV_UP_NONE && stride != 1) return dv_fail(DV_ERR_INVALID, "%s: upsampling runs with stride 1 only", what);
+  if (c_sc > 0 && (stride != 1 || up_mode != DV_UP_NONE)) return dv_fail(DV_ERR_INVALID, "%s: the second k-segment needs stride 1 and no upsampling (its rows are gathered like the first's)", what);
+  if (c_sc % 32 != 0) return dv_fail(DV_ERR_INVALID, "%s: source widths %d, %d and %d must be multiples of 32 (the k-tile)", what, c0, c1, c_sc);
+  if (2 * (size_t)c_sc + 256 > DV_ZERO_PAGE_BYTES) return dv_fail(DV_ERR_INVALID, "%s: a source of %d channels exceeds the %d one source tensor may have", what, c_sc, (DV_ZERO_PAGE_BYTES - 256) / 2);
+  if ((tile & GT_BK64) && c_sc % 64 != 0) return dv_fail(DV_ERR_INVALID, "%s: 64-deep k-tiles need source widths that are multiples of 64, not %d", what, c_sc);
+  const int pad = (taps - 1) / 2;
+  const int T_virt = up_mode == DV_UP_X2 ? 2 * T : (up_mode == DV_UP_SIZE ? up_T : T);
+  const int Tv_out = (T_virt + 2 * pad - taps) / stride + 1;
+  if (Tp_out < Tv_out) return dv_fail(DV_ERR_INVALID, "%s: Tp_out = %d < the %d output frames", what, Tp_out, Tv_out);
+  if ((long long)B * Tp_out > 32768) return dv_fail(DV_ERR_INVALID, "%s: B x Tp_out = %lld rows: at most 32768", what, (long long)B * Tp_out);
+  if (with_stats && (Cout % 16 != 0 || Tp_out % 32 != 0 || Tv_out <= Tp_out - 32))
+    return dv_fail(DV_ERR_INVALID, "%s: stats16 needs Cout %% 16 == 0 and Tp_out = the %d frames rounded up to 32, not Cout = %d, Tp_out = %d", what, Tv_out, Cout, Tp_out);
+  // (tile, precision, the widths of [a0 | a1]: op_gemm's checks on the same launch shape)
+  if (int rc = gemm_op_shape(g, B * Tp_out, c0 + c1, Cout, c1 > 0 ? c0 : 0, DV_GEMM_STORE, tile, 0, precision, what)) return rc;
+  g.seg[0].taps = taps; g.seg[0].pad = pad;
+  if (c_sc > 0) { g.seg[1].c0 = c_sc; g.seg[1].taps = 1; g.seg[1].pad = 0; g.nseg = 2; }
+  g.B = B; g.T_in = Tp_in; g.Tv_in = T; g.T_virt = T_virt; g.Tv_out = Tv_out; g.T_out = Tp_out;
+  g.stride = stride; g.up_mode = up_mode;
+  g.up_scale = up_mode == DV_UP_SIZE ? (float)T / (float)up_T : 1.f;
+  g.Kp = taps * (c0 + c1) + c_sc; g.ldo = Cout;
+  return DV_OK;
+}
+
+extern "C" int dv_op_conv_rows_variant(int32_t B, int32_t T, int32_t Tp_in, int32_t c0, int32_t c1, int32_t c_sc, int32_t Cout, int32_t taps,
+                                       int32_t stride, int32_t up_mode, int32_t up_T, int32_t Tp_out, int32_t tile, int32_t precision,
+                                       int32_t* variant, int32_t* tile_kind, int32_t* nsplit, int32_t* candidates, int32_t cap) {
+  const char* what = "dv_op_conv_rows_variant";
+  if (!variant || !tile_kind || !nsplit || cap < 0 || (cap > 0 && !candidates)) return dv_fail(DV_ERR_INVALID, "%s: null argument", what);
+  GemmParams g;
+  if (int rc = conv_rows_shape(g, B, T, Tp_in, c0, c1, c_sc, Cout, taps, stride, up_mode, up_T, Tp_out, 0, tile, precision, what)) return rc;
+  const int v = gemm_variant(g);
+  const int kind = gemm_variant_tile(g, v);
+  if (v < 0 || kind < 0) return dv_fail(DV_ERR_INVALID, "%s: no instantiation for tile 0x%x", what, tile);
+  *variant = v; *tile_kind = kind; *nsplit = precision == DV_PREC_BF16X3 ? 3 : 1;
+  int cand[16];
+  const int n = gemm_candidates(g, cand, 16);
+  for (int i = 0; i < cap; ++i) candidates[i] = i < n ? cand[i] : 0;   // (0 = DV_GT_AUTO ends the list)
+  return DV_OK;
+}
+
+extern "C" int dv_op_conv_rows(const float* x0, const float* x1, const float* w, const float* bias, const float* x_sc, const float* w_sc,
+                               float* y, uint16_t* y_hi, uint16_t* y_lo, float* stats16, int32_t B, int32_t T, int32_t Tp_in, int32_t c0,
+                               int32_t c1, int32_t c_sc, int32_t Cout, int32_t taps, int32_t stride, int32_t up_mode, int32_t up_T,
+                               int32_t Tp_out, int32_t tile, int32_t precision, void* stream) {
+  const char* what = "dv_op_conv_rows";
+  GemmParams g;
+  if (int rc = conv_rows_shape(g, B, T, Tp_in, c0, c1, c_sc, Cout, taps, stride, up_mode, up_T, Tp_out, stats16 != nullptr, tile, precision, what)) return rc;
+  const bool x3 = precision == DV_PREC_BF16X3;
+  if (!x0 || !w || (!y && !y_hi)) return dv_fail(DV_ERR_INVALID, "%s: x0, w and an output (y and / or y_hi) are required", what);
+  if ((c1 > 0) != (x1 != nullptr)) return dv_fail(DV_ERR_INVALID, "%s: x1 goes with c1 > 0, and only with it", what);
+  if (c_sc > 0 ? (!x_sc || !w_sc) : (x_sc || w_sc)) return dv_fail(DV_ERR_INVALID, "%s: x_sc and w_sc go with c_sc > 0, and only with it", what);
+  if (y_hi && x3 && !y_lo) return dv_fail(DV_ERR_INVALID, "%s: bf16x3 plane output needs y_lo", what);
+  if (!y_hi && y_lo) return dv_fail(DV_ERR_INVALID, "%s: y_lo without y_hi", what);
+  if (!al16(y) || !al16(y_hi) || !al16(y_lo) || !al16(x0) || !al16(x1) || !al16(x_sc) || !al16(stats16))
+    return dv_fail(DV_ERR_INVALID, "%s: the sources and the outputs must be 16-byte aligned", what);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(gemm_init());
+  gemm_env_refresh();
+  HIPCHK(attn_init());
+  const int Kp = g.Kp, Npad = g.N_pad, cin = c0 + c1;
+  const size_t rows = (size_t)B * Tp_in;
+  OpScratch sc;
+  // every operand plane: [B * Tp_in rows | CONV_ROWS_GUARD rows of bf16 NaN] - a gather that runs past the last utterance shows
+  const int widths[3] = {c0, c1, c_sc};
+  const float* srcs[3] = {x0, x1, x_sc};
+  bf16_t* ph[3] = {nullptr, nullptr, nullptr}; bf16_t* pl[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; ++i) {
+    if (widths[i] == 0) continue;
+    const size_t el = rows * widths[i], gel = (size_t)CONV_ROWS_GUARD * widths[i];
+    ph[i] = sc.get<bf16_t>((el + gel) * 2, st, false);
+    pl[i] = x3 ? sc.get<bf16_t>((el + gel) * 2, st, false) : nullptr;
+    if (!ph[i] || (x3 && !pl[i])) return dv_fail(DV_ERR_HIP, "%s: hipMalloc failed", what);
+    HIPCHK(launch_split(srcs[i], ph[i], pl[i], (int64_t)el, st));
+    HIPCHK(hipMemsetD16Async((hipDeviceptr_t)(ph[i] + el), 0x7fc1, gel, st));
+    if (pl[i]) HIPCHK(hipMemsetD16Async((hipDeviceptr_t)(pl[i] + el), 0x7fc1, gel, st));
+  }
+  bf16_t* hi = sc.get<bf16_t>((size_t)Npad * Kp * 2, st, true);
+  bf16_t* lo = x3 ? sc.get<bf16_t>((size_t)Npad * Kp * 2, st, true) : nullptr;
+  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
+  if (!hi || !zp || (x3 && !lo)) return dv_fail(DV_ERR_HIP, "%s: hipMalloc failed", what);
+  PackSpec s{};
+  s.src = w; s.N = Cout; s.kind = 1; s.C = cin; s.taps = taps; s.c_pad = cin; s.k_off = 0; s.n_off = 0;
+  HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
+  if (c_sc > 0) {
+    s.src = w_sc; s.C = c_sc; s.taps = 1; s.c_pad = c_sc; s.k_off = taps * cin;
+    HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
+  }
+  g.seg[0].a0_hi = ph[0]; g.seg[0].a0_lo = pl[0]; g.seg[0].a1_hi = ph[1]; g.seg[0].a1_lo = pl[1];
+  g.seg[1].a0_hi = ph[2]; g.seg[1].a0_lo = pl[2];
+  g.w_hi = hi; g.w_lo = lo; g.bias = bias; g.zero_page = zp;
+  g.out = y; g.out_hi = reinterpret_cast<bf16_t*>(y_hi); g.out_lo = x3 ? reinterpret_cast<bf16_t*>(y_lo) : nullptr; g.stats16 = stats16;
+  hipError_t e = launch_gemm(g, precision, st);   // (no fragment-major weights: always k_gemm)
+  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+  HIPCHK(hipStreamSynchronize(st));
+  return DV_OK;
+}
+
 extern "C" int dv_op_group_stats(const float* x, float* mean, float* rstd, int32_t B, int32_t T, int32_t C, int32_t groups,
                                  float eps, void* stream) {
   if (!x || !mean || !rstd || C % groups != 0 || (C / groups) % 4 != 0 || groups > 64)

@@ -636,6 +636,31 @@ int dv_op_gemm(const float* x, const float* w, const float* bias, const float* r
  * k-step) or 1 (single bf16). */
 int dv_op_gemm_variant(int32_t M, int32_t K, int32_t N, int32_t K0, int32_t epi, int32_t tile, int32_t splitk, int32_t precision,
                        int32_t* variant, int32_t* tile_kind, int32_t* nsplit);
+/* k_gemm as the implicit-GEMM convolution of the forward (Downsample2D, the size-forced Upsample2D, every convolution the
+ * resident-operand kernels refuse), on CHANNELS-LAST tensors in a padded row space: T frames of each of the B utterances exist,
+ * Tp_in >= T is the row pitch of the sources, Tp_out >= the output frames that of the result (any value).
+ *   sources  x0 [B, Tp_in, c0] and, with c1 > 0, x1 [B, Tp_in, c1]: the channel concatenation [x0 | x1]; rows [T, Tp_in) may hold
+ *            anything finite and reach no output.  w [Cout, c0 + c1, taps], taps 1 or 3, padding (taps - 1) / 2; bias [Cout] or NULL.
+ *   c_sc > 0 + the 1x1 convolution w_sc [Cout, c_sc, 1] of x_sc [B, Tp_in, c_sc] as a second k-segment; stride 1, DV_UP_NONE only.
+ *   mode     stride 1 or 2; up_mode DV_UP_NONE, DV_UP_X2 (nearest to 2 T frames) or DV_UP_SIZE (nearest to up_T frames: source frame
+ *            min(floor((float)t * ((float)T / (float)up_T)), T - 1), ATen's rule); upsampling with stride 1 only, up_T = 0 otherwise.
+ *            Output frames Tv_out = (T_virt + 2 padding - taps) / stride + 1, T_virt = T, 2 T or up_T.
+ *   outputs  fp32 y and / or split bf16 planes y_hi, y_lo (as dv_op_gemm), [B, Tp_out, Cout]: rows [Tv_out, Tp_out) of every utterance
+ *            are written as zeros.  stats16 (or NULL): [B * Tp_out / 32, Cout / 16, 2] (sum, squared deviations from the block's own
+ *            mean) over the rows that exist of every 32 x 16 block; needs Cout % 16 == 0 and Tp_out = Tv_out rounded up to 32.
+ *   tile     as dv_op_gemm; every source width (c0, c1, c_sc) a multiple of 32, of 64 with DV_GT_BK64.  B * Tp_out <= 32768.
+ * The operand planes the kernel reads are followed by 32 rows of NaN.  No fragment-major weights are made: the launch always runs on
+ * k_gemm.  Every argument is checked before anything is launched (DV_ERR_INVALID with a message); returns after the stream has drained. */
+enum { DV_UP_NONE = 0, DV_UP_X2 = 1, DV_UP_SIZE = 2 };
+int dv_op_conv_rows(const float* x0, const float* x1, const float* w, const float* bias, const float* x_sc, const float* w_sc, float* y,
+                    uint16_t* y_hi, uint16_t* y_lo, float* stats16, int32_t B, int32_t T, int32_t Tp_in, int32_t c0, int32_t c1,
+                    int32_t c_sc, int32_t Cout, int32_t taps, int32_t stride, int32_t up_mode, int32_t up_T, int32_t Tp_out, int32_t tile,
+                    int32_t precision, void* stream);
+/* Which instantiation dv_op_conv_rows would launch (host only, the same shape checks; as dv_op_gemm_variant), and the forced tiles the
+ * prepare-time tuner would try on this launch: candidates[0 .. cap) receives them, DV_GT_AUTO (0) behind the last (cap 0: none). */
+int dv_op_conv_rows_variant(int32_t B, int32_t T, int32_t Tp_in, int32_t c0, int32_t c1, int32_t c_sc, int32_t Cout, int32_t taps,
+                            int32_t stride, int32_t up_mode, int32_t up_T, int32_t Tp_out, int32_t tile, int32_t precision,
+                            int32_t* variant, int32_t* tile_kind, int32_t* nsplit, int32_t* candidates, int32_t cap);
 /* GroupNorm statistics over a channels-last tensor x[B*T, C]: mean/rstd [B, groups]. */
 int dv_op_group_stats(const float* x, float* mean, float* rstd, int32_t B, int32_t T, int32_t C, int32_t groups,
                       float eps, void* stream);
