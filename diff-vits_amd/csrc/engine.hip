@@ -2746,692 +2746,3 @@ extern "C" int dv_penc_probe(dv_penc* p, const char* name, float* host_out, int6
   if (!p->core.prepared) return dv_fail(DV_ERR_STATE, "dv_penc_probe before dv_penc_prepare");
   return probe_copy(&p->core, name, host_out, capacity, dims);
 }
-
-// ----------------------------------------------------------------------------- single-operator entry points
-// scratch for the single-operator entry points
-struct OpScratch {
-  std::vector<void*> ptrs;
-  ~OpScratch() { for (void* p : ptrs) (void)hipFree(p); }
-  template <typename T> T* get(size_t bytes, hipStream_t st, bool zero) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    ptrs.push_back(p);
-    if (zero) (void)hipMemsetAsync(p, 0, bytes ? bytes : 16, st);
-    else if (poison_fill(p, bytes ? bytes : 16, st) != hipSuccess) return nullptr;   // (DVITS_POISON)
-    return reinterpret_cast<T*>(p);
-  }
-};
-
-extern "C" int dv_op_conv1d(const float* x, const float* w, const float* bias, float* y, int32_t B, int32_t Cin, int32_t T,
-                            int32_t Cout, int32_t k, int32_t stride, int32_t up_T, int32_t precision, void* stream) {
-  if (!x || !w || !y || (k != 1 && k != 3) || (stride != 1 && stride != 2)) return dv_fail(DV_ERR_INVALID, "dv_op_conv1d: bad argument");
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(gemm_init());
-  gemm_env_refresh();
-  HIPCHK(attn_init());
-  const bool x3 = precision == DV_PREC_BF16X3;
-  const int cpad = rup(Cin, 32), Kp = k * cpad, Npad = rup(Cout, 128);
-  if (2 * (size_t)cpad + 256 > DV_ZERO_PAGE_BYTES)
-    return dv_fail(DV_ERR_INVALID, "dv_op_conv1d: Cin = %d exceeds the %d channels one source tensor may have", Cin, (DV_ZERO_PAGE_BYTES - 256) / 2);
-  OpScratch sc;
-  bf16_t* xh = sc.get<bf16_t>((size_t)B * T * cpad * 2, st, false);
-  bf16_t* xl = x3 ? sc.get<bf16_t>((size_t)B * T * cpad * 2, st, false) : nullptr;
-  bf16_t* hi = sc.get<bf16_t>((size_t)Npad * Kp * 2, st, true);
-  bf16_t* lo = x3 ? sc.get<bf16_t>((size_t)Npad * Kp * 2, st, true) : nullptr;
-  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
-  if (!xh || !hi || !zp || (x3 && (!xl || !lo))) return dv_fail(DV_ERR_HIP, "dv_op_conv1d: hipMalloc failed");
-  HIPCHK(launch_pack_input(x, Cin, nullptr, 0, xh, xl, cpad, B, T, st));
-  PackSpec s{};
-  s.src = w; s.N = Cout; s.kind = 1; s.C = Cin; s.taps = k; s.c_pad = cpad; s.k_off = 0; s.n_off = 0;
-  HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
-  GemmParams g{};
-  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl; g.seg[0].c0 = cpad; g.seg[0].taps = k; g.seg[0].pad = (k - 1) / 2;
-  g.nseg = 1; g.B = B; g.T_in = T;
-  g.T_virt = up_T > 0 ? up_T : T;
-  g.up_mode = up_T > 0 ? UP_SIZE : UP_NONE;
-  g.up_scale = up_T > 0 ? (float)T / (float)up_T : 1.f;
-  g.stride = stride;
-  g.T_out = (g.T_virt + 2 * g.seg[0].pad - k) / stride + 1;
-  g.w_hi = hi; g.w_lo = lo; g.Kp = Kp; g.N_pad = Npad; g.bias = bias;
-  g.M = B * g.T_out; g.N = Cout; g.epi = EPI_STORE_NCT; g.out = y; g.ldo = Cout; g.zero_page = zp;
-  HIPCHK(launch_gemm(g, precision, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-// y = x W^T + bias through k_gemm; output as fp32 [M, ldo] (y) and / or split bf16 planes [M, ldo] (y_hi, y_lo);
-// geglu: W = [value rows | gate rows] (N = 2 x N_out, reference activations GEGLU: hidden * gelu(gate)), output N / 2 columns
-static int op_linear(const float* x, const float* w, const float* bias, float* y, bf16_t* y_hi, bf16_t* y_lo, int M, int K, int N, int ldo,
-                     int geglu, int precision, hipStream_t st, const char* what) {
-  if (!x || !w || (!y && !y_hi) || K % 32 != 0) return dv_fail(DV_ERR_INVALID, "%s: K must be a multiple of 32 (and an output is needed)", what);
-  if (geglu && (N % 64 != 0 || y)) return dv_fail(DV_ERR_INVALID, "%s: GEGLU needs N %% 64 == 0 and writes planes only", what);
-  const int n_out = geglu ? N / 2 : N;
-  if (ldo < n_out) return dv_fail(DV_ERR_INVALID, "%s: ldo %d < %d output columns", what, ldo, n_out);
-  if (2 * (size_t)K + 256 > DV_ZERO_PAGE_BYTES) return dv_fail(DV_ERR_INVALID, "%s: K = %d exceeds the %d channels one source tensor may have", what, K, (DV_ZERO_PAGE_BYTES - 256) / 2);
-  HIPCHK(gemm_init());
-  gemm_env_refresh();
-  HIPCHK(attn_init());
-  const bool x3 = precision == DV_PREC_BF16X3;
-  const int Npad = rup(N, 128);
-  OpScratch sc;
-  bf16_t* xh = sc.get<bf16_t>((size_t)M * K * 2, st, false);
-  bf16_t* xl = x3 ? sc.get<bf16_t>((size_t)M * K * 2, st, false) : nullptr;
-  bf16_t* hi = sc.get<bf16_t>((size_t)Npad * K * 2, st, true);
-  bf16_t* lo = x3 ? sc.get<bf16_t>((size_t)Npad * K * 2, st, true) : nullptr;
-  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
-  float* pb = (geglu && bias) ? sc.get<float>((size_t)Npad * 4, st, true) : nullptr;
-  if (!xh || !hi || !zp || (x3 && (!xl || !lo)) || (geglu && bias && !pb)) return dv_fail(DV_ERR_HIP, "%s: hipMalloc failed", what);
-  HIPCHK(launch_split(x, xh, xl, (int64_t)M * K, st));
-  PackSpec s{};
-  s.src = w; s.N = N; s.kind = 0; s.C = K; s.taps = 1; s.c_pad = K; s.geglu = geglu;
-  HIPCHK(launch_pack_weight(s, hi, lo, K, st));
-  if (pb) HIPCHK(launch_fold_bias(nullptr, bias, nullptr, pb, N, K, 0, 1, st));   // bias in the packed [32 a | 32 gate] column order
-  GemmParams g{};
-  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl; g.seg[0].c0 = K; g.seg[0].taps = 1;
-  g.nseg = 1; g.B = 1; g.T_in = g.T_out = g.T_virt = M; g.stride = 1;
-  g.w_hi = hi; g.w_lo = lo; g.Kp = K; g.N_pad = Npad; g.bias = geglu ? pb : bias;
-  g.M = M; g.N = N; g.epi = geglu ? EPI_GEGLU : EPI_STORE; g.out = y; g.out_hi = y_hi; g.out_lo = y_lo; g.ldo = ldo; g.zero_page = zp;
-  hipError_t e = launch_gemm(g, precision, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-extern "C" int dv_op_linear(const float* x, const float* w, const float* bias, float* y, int32_t M, int32_t K, int32_t N,
-                            int32_t precision, void* stream) {
-  return op_linear(x, w, bias, y, nullptr, nullptr, M, K, N, N, 0, precision, (hipStream_t)stream, "dv_op_linear");
-}
-
-extern "C" int dv_op_linear_planes(const float* x, const float* w, const float* bias, float* y, uint16_t* y_hi, uint16_t* y_lo, int32_t M,
-                                   int32_t K, int32_t N, int32_t ldo, int32_t geglu, int32_t precision, void* stream) {
-  if (!y_hi || (precision == DV_PREC_BF16X3 && !y_lo)) return dv_fail(DV_ERR_INVALID, "dv_op_linear_planes: plane outputs are required");
-  return op_linear(x, w, bias, y, y_hi, precision == DV_PREC_BF16X3 ? y_lo : nullptr, M, K, N, ldo, geglu, precision, (hipStream_t)stream,
-                   "dv_op_linear_planes");
-}
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// ---- dv_op_gemm: k_gemm on a chosen menu entry, k-split form, epilogue and source layout (include/dvits_hip.h) ----
-static_assert(DV_GT_AUTO == GT_AUTO && DV_GT_T0 == GT_T0 && DV_GT_T1 == GT_T1 && DV_GT_T2 == GT_T2 && DV_GT_T2S == GT_T2S && DV_GT_T2G == GT_T2G &&
-              DV_GT_T3 == GT_T3 && DV_GT_T4 == GT_T4 && DV_GT_T4G == GT_T4G && DV_GT_T0S == GT_T0S && DV_GT_BK64 == GT_BK64, "public tile ids");
-static_assert(DV_GEMM_STORE == EPI_STORE && DV_GEMM_RESIDUAL == EPI_RESIDUAL && DV_GEMM_GEGLU == EPI_GEGLU, "public epilogue ids");
-
-// Checks everything launch_gemm / k_gemm need of the shape and fills the host-only fields of g (no pointers, nothing launched): the
-// requirements are read from gemm_tile.h and launch_gemm, never found by launching.  0, or DV_ERR_INVALID with the message set.
-static int gemm_op_shape(GemmParams& g, int M, int K, int N, int K0, int epi, int tile, int splitk, int precision, const char* what) {
-  if (M <= 0 || N <= 0 || K <= 0 || M > 32768 || N > 32768) return dv_fail(DV_ERR_INVALID, "%s: M = %d, N = %d, K = %d: 1 .. 32768 rows and columns", what, M, N, K);
-  if (precision != DV_PREC_BF16X3 && precision != DV_PREC_BF16) return dv_fail(DV_ERR_INVALID, "%s: precision %d is not a DV_PREC_*", what, precision);
-  if (epi != DV_GEMM_STORE && epi != DV_GEMM_RESIDUAL && epi != DV_GEMM_GEGLU) return dv_fail(DV_ERR_INVALID, "%s: epilogue %d is not a DV_GEMM_*", what, epi);
-  if (K0 < 0 || K0 >= K) return dv_fail(DV_ERR_INVALID, "%s: K0 = %d must be 0 or inside (0, K = %d)", what, K0, K);
-  const int c0 = K0 > 0 ? K0 : K, c1 = K0 > 0 ? K - K0 : 0;
-  if (c0 % 32 != 0 || c1 % 32 != 0) return dv_fail(DV_ERR_INVALID, "%s: source widths %d and %d must be multiples of 32 (the k-tile)", what, c0, c1);
-  if (2 * (size_t)c0 + 256 > DV_ZERO_PAGE_BYTES || 2 * (size_t)c1 + 256 > DV_ZERO_PAGE_BYTES)
-    return dv_fail(DV_ERR_INVALID, "%s: a source of %d channels exceeds the %d one source tensor may have", what, c0 > c1 ? c0 : c1, (DV_ZERO_PAGE_BYTES - 256) / 2);
-  const int ft = tile & 0xff;
-  if ((tile & ~(0xff | GT_BK64)) != 0 || ft > GT_T0S || (ft == GT_AUTO && tile != 0)) return dv_fail(DV_ERR_INVALID, "%s: tile 0x%x is not 0 or a DV_GT_* id (| DV_GT_BK64)", what, tile);
-  if (tile & GT_BK64) {
-    if (ft == GT_T0 || ft == GT_T0S) return dv_fail(DV_ERR_INVALID, "%s: the 128x128 tiles exist with 32-deep k-tiles only", what);
-    if (c0 % 64 != 0 || c1 % 64 != 0) return dv_fail(DV_ERR_INVALID, "%s: 64-deep k-tiles need source widths that are multiples of 64, not %d and %d", what, c0, c1);
-  }
-  if (epi == DV_GEMM_GEGLU) {
-    if (N % 64 != 0) return dv_fail(DV_ERR_INVALID, "%s: GEGLU needs N %% 64 == 0 ([32 value | 32 gate] column blocks), not N = %d", what, N);
-    if (ft != GT_AUTO && !gemm_tile_geglu_ok(ft)) return dv_fail(DV_ERR_INVALID, "%s: GEGLU needs a tile with a 64-column block per wave (T0, T0S, T1, T2G, T4G), not tile %d", what, ft);
-  }
-  const int fused = splitk & DV_GEMM_SPLITK_FUSED, slices = splitk & ~DV_GEMM_SPLITK_FUSED;
-  if (splitk != 0) {
-    if (fused ? slices != 2 : (slices != 2 && slices != 3)) return dv_fail(DV_ERR_INVALID, "%s: splitk 0x%x: 2 or 3 slices in two launches, or 2 | DV_GEMM_SPLITK_FUSED", what, splitk);
-    if (epi == DV_GEMM_GEGLU) return dv_fail(DV_ERR_INVALID, "%s: split-K runs the store and residual epilogues only (gemm_splitk_plan)", what);
-    if (K / 64 < slices) return dv_fail(DV_ERR_INVALID, "%s: K = %d has fewer 64-deep k-tiles than the %d slices", what, K, slices);
-    if (fused && ((M + 31) / 32) * ((N + 31) / 32) > 4096) return dv_fail(DV_ERR_INVALID, "%s: the fused pair has 4096 tile counters; M = %d, N = %d need more", what, M, N);
-  }
-  g = GemmParams{};
-  g.seg[0].c0 = c0; g.seg[0].c1 = c1; g.seg[0].taps = 1;
-  g.nseg = 1; g.B = 1; g.T_in = g.T_out = g.T_virt = M; g.stride = 1;
-  g.Kp = K; g.N_pad = rup(N, 128); g.M = M; g.N = N; g.epi = epi; g.force_tile = tile;
-  return DV_OK;
-}
-
-extern "C" int dv_op_gemm_variant(int32_t M, int32_t K, int32_t N, int32_t K0, int32_t epi, int32_t tile, int32_t splitk, int32_t precision,
-                                  int32_t* variant, int32_t* tile_kind, int32_t* nsplit) {
-  if (!variant || !tile_kind || !nsplit) return dv_fail(DV_ERR_INVALID, "dv_op_gemm_variant: null argument");
-  GemmParams g;
-  if (int rc = gemm_op_shape(g, M, K, N, K0, epi, tile, splitk, precision, "dv_op_gemm_variant")) return rc;
-  const int v = gemm_variant(g);
-  const int kind = gemm_variant_tile(g, v);
-  if (v < 0 || kind < 0) return dv_fail(DV_ERR_INVALID, "dv_op_gemm_variant: no instantiation for tile 0x%x", tile);
-  *variant = v; *tile_kind = kind; *nsplit = precision == DV_PREC_BF16X3 ? 3 : 1;
-  return DV_OK;
-}
-
-extern "C" int dv_op_gemm(const float* x, const float* w, const float* bias, const float* res, const float* rowmask, float* y, uint16_t* y_hi,
-                          uint16_t* y_lo, int32_t M, int32_t K, int32_t N, int32_t K0, int32_t ldo, int32_t ldres, int32_t epi, int32_t relu,
-                          int32_t tile, int32_t splitk, int32_t precision, void* stream) {
-  const char* what = "dv_op_gemm";
-  GemmParams g;
-  if (int rc = gemm_op_shape(g, M, K, N, K0, epi, tile, splitk, precision, what)) return rc;
-  const bool x3 = precision == DV_PREC_BF16X3;
-  if (!x || !w || (!y && !y_hi)) return dv_fail(DV_ERR_INVALID, "%s: x, w and an output (y and / or y_hi) are required", what);
-  if (y_hi && x3 && !y_lo) return dv_fail(DV_ERR_INVALID, "%s: bf16x3 plane output needs y_lo", what);
-  if (!y_hi && y_lo) return dv_fail(DV_ERR_INVALID, "%s: y_lo without y_hi", what);
-  const int n_out = epi == DV_GEMM_GEGLU ? N / 2 : N;
-  if (ldo < n_out) return dv_fail(DV_ERR_INVALID, "%s: ldo %d < %d output columns", what, ldo, n_out);
-  if (epi == DV_GEMM_RESIDUAL ? (!res || ldres < N) : (res != nullptr)) return dv_fail(DV_ERR_INVALID, "%s: res [M, ldres >= N] goes with DV_GEMM_RESIDUAL, and only with it", what);
-  if (relu != 0 && relu != 1) return dv_fail(DV_ERR_INVALID, "%s: relu is 0 or 1", what);
-  if (epi == DV_GEMM_GEGLU && (relu || rowmask)) return dv_fail(DV_ERR_INVALID, "%s: the GEGLU epilogue has no ReLU / row mask", what);
-  // 16-byte epilogue accesses are taken on the pitches alone (gemm_tile.h vec4 / al8): the bases must allow them
-  if (!al16(y) || !al16(res) || !al16(y_hi) || !al16(y_lo) || !al16(x)) return dv_fail(DV_ERR_INVALID, "%s: x, res and the outputs must be 16-byte aligned", what);
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(gemm_init());
-  gemm_env_refresh();
-  HIPCHK(attn_init());
-  const int c0 = g.seg[0].c0, c1 = g.seg[0].c1, Npad = g.N_pad;
-  const int fused = splitk & DV_GEMM_SPLITK_FUSED, slices = splitk & ~DV_GEMM_SPLITK_FUSED;
-  OpScratch sc;
-  bf16_t* xh = sc.get<bf16_t>((size_t)M * K * 2, st, false);
-  bf16_t* xl = x3 ? sc.get<bf16_t>((size_t)M * K * 2, st, false) : nullptr;
-  bf16_t* hi = sc.get<bf16_t>((size_t)Npad * K * 2, st, true);
-  bf16_t* lo = x3 ? sc.get<bf16_t>((size_t)Npad * K * 2, st, true) : nullptr;
-  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
-  const bool geglu = epi == DV_GEMM_GEGLU;
-  float* pb = (geglu && bias) ? sc.get<float>((size_t)Npad * 4, st, true) : nullptr;
-  float* xs = c1 > 0 ? sc.get<float>((size_t)M * K * 4, st, false) : nullptr;   // the two sources, each contiguous: [M, c0] then [M, c1]
-  float* skb = slices ? sc.get<float>(gemm_splitk_bytes(M, N, slices), st, false) : nullptr;
-  unsigned* skt = fused ? sc.get<unsigned>(4096 * sizeof(unsigned), st, true) : nullptr;
-  if (!xh || !hi || !zp || (x3 && (!xl || !lo)) || (geglu && bias && !pb) || (c1 > 0 && !xs) || (slices && !skb) || (fused && !skt))
-    return dv_fail(DV_ERR_HIP, "%s: hipMalloc failed", what);
-  if (c1 > 0) {
-    HIPCHK(hipMemcpy2DAsync(xs, (size_t)c0 * 4, x, (size_t)K * 4, (size_t)c0 * 4, M, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpy2DAsync(xs + (size_t)M * c0, (size_t)c1 * 4, x + c0, (size_t)K * 4, (size_t)c1 * 4, M, hipMemcpyDeviceToDevice, st));
-    HIPCHK(launch_split(xs, xh, xl, (int64_t)M * K, st));     // (elementwise: the planes keep the [M, c0] | [M, c1] layout)
-  } else {
-    HIPCHK(launch_split(x, xh, xl, (int64_t)M * K, st));
-  }
-  PackSpec s{};
-  s.src = w; s.N = N; s.kind = 0; s.C = K; s.taps = 1; s.c_pad = K; s.geglu = geglu;
-  HIPCHK(launch_pack_weight(s, hi, lo, K, st));
-  if (pb) HIPCHK(launch_fold_bias(nullptr, bias, nullptr, pb, N, K, 0, 1, st));   // bias in the packed [32 value | 32 gate] column order
-  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl;
-  if (c1 > 0) { g.seg[0].a1_hi = xh + (size_t)M * c0; g.seg[0].a1_lo = xl ? xl + (size_t)M * c0 : nullptr; }
-  g.w_hi = hi; g.w_lo = lo; g.bias = geglu ? pb : bias; g.zero_page = zp;
-  g.res = res; g.ldres = ldres; g.relu = relu; g.rowmask = rowmask;
-  g.out = y; g.out_hi = reinterpret_cast<bf16_t*>(y_hi); g.out_lo = x3 ? reinterpret_cast<bf16_t*>(y_lo) : nullptr; g.ldo = ldo;
-  if (slices) { g.sk_buf = skb; g.sk_split = slices; g.sk_ticket = skt; }
-  hipError_t e = launch_gemm(g, precision, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-// ---- dv_op_conv_rows: k_gemm's convolution operand path (gemm_tile.h prep_a / advance / utt_of) as Builder::resample and the resnet
-// fallback launch it: channels-last sources in a padded row space, taps, stride 2, nearest upsampling, [a0 | a1], a second k-segment ----
-static_assert(DV_UP_NONE == UP_NONE && DV_UP_X2 == UP_X2 && DV_UP_SIZE == UP_SIZE, "public upsampling modes");
-constexpr int CONV_ROWS_GUARD = 32;   // rows of NaN behind every operand plane the kernel reads
-
-// Checks the shape and fills the host-only fields of g (no pointers, nothing launched).  0, or DV_ERR_INVALID with the message set.
-static int conv_rows_shape(GemmParams& g, int B, int T, int Tp_in, int c0, int c1, int c_sc, int Cout, int taps, int stride, int up_mode,
-                           int up_T, int Tp_out, int with_stats, int tile, int precision, const char* what) {
-  if (B <= 0 || T <= 0 || Tp_in < T || Tp_in > 32768 || c0 <= 0 || c1 < 0 || c_sc < 0 || Cout <= 0 || Tp_out <= 0 || Tp_out > 32768)
-    return dv_fail(DV_ERR_INVALID, "%s: B = %d, T = %d, Tp_in = %d, c0 = %d, c1 = %d, c_sc = %d, Cout = %d, Tp_out = %d: positive sizes, T <= Tp_in <= 32768", what, B, T, Tp_in, c0, c1, c_sc, Cout, Tp_out);
-  if (taps != 1 && taps != 3) return dv_fail(DV_ERR_INVALID, "%s: taps = %d is not 1 or 3", what, taps);
-  if (stride != 1 && stride != 2) return dv_fail(DV_ERR_INVALID, "%s: stride = %d is not 1 or 2", what, stride);
-  if (up_mode != DV_UP_NONE && up_mode != DV_UP_X2 && up_mode != DV_UP_SIZE) return dv_fail(DV_ERR_INVALID, "%s: up_mode %d is not a DV_UP_*", what, up_mode);
-  if (up_mode == DV_UP_SIZE ? (up_T <= 0 || up_T > 32768) : up_T != 0) return dv_fail(DV_ERR_INVALID, "%s: up_T = %d goes with DV_UP_SIZE (1 .. 32768 frames), and only with it", what, up_T);
-  if (up_mode != DV_UP_NONE && stride != 1) return dv_fail(DV_ERR_INVALID, "%s: upsampling runs with stride 1 only", what);
-  if (c_sc > 0 && (stride != 1 || up_mode != DV_UP_NONE)) return dv_fail(DV_ERR_INVALID, "%s: the second k-segment needs stride 1 and no upsampling (its rows are gathered like the first's)", what);
-  if (c_sc % 32 != 0) return dv_fail(DV_ERR_INVALID, "%s: source widths %d, %d and %d must be multiples of 32 (the k-tile)", what, c0, c1, c_sc);
-  if (2 * (size_t)c_sc + 256 > DV_ZERO_PAGE_BYTES) return dv_fail(DV_ERR_INVALID, "%s: a source of %d channels exceeds the %d one source tensor may have", what, c_sc, (DV_ZERO_PAGE_BYTES - 256) / 2);
-  if ((tile & GT_BK64) && c_sc % 64 != 0) return dv_fail(DV_ERR_INVALID, "%s: 64-deep k-tiles need source widths that are multiples of 64, not %d", what, c_sc);
-  const int pad = (taps - 1) / 2;
-  const int T_virt = up_mode == DV_UP_X2 ? 2 * T : (up_mode == DV_UP_SIZE ? up_T : T);
-  const int Tv_out = (T_virt + 2 * pad - taps) / stride + 1;
-  if (Tp_out < Tv_out) return dv_fail(DV_ERR_INVALID, "%s: Tp_out = %d < the %d output frames", what, Tp_out, Tv_out);
-  if ((long long)B * Tp_out > 32768) return dv_fail(DV_ERR_INVALID, "%s: B x Tp_out = %lld rows: at most 32768", what, (long long)B * Tp_out);
-  if (with_stats && (Cout % 16 != 0 || Tp_out % 32 != 0 || Tv_out <= Tp_out - 32))
-    return dv_fail(DV_ERR_INVALID, "%s: stats16 needs Cout %% 16 == 0 and Tp_out = the %d frames rounded up to 32, not Cout = %d, Tp_out = %d", what, Tv_out, Cout, Tp_out);
-  // (tile, precision, the widths of [a0 | a1]: op_gemm's checks on the same launch shape)
-  if (int rc = gemm_op_shape(g, B * Tp_out, c0 + c1, Cout, c1 > 0 ? c0 : 0, DV_GEMM_STORE, tile, 0, precision, what)) return rc;
-  g.seg[0].taps = taps; g.seg[0].pad = pad;
-  if (c_sc > 0) { g.seg[1].c0 = c_sc; g.seg[1].taps = 1; g.seg[1].pad = 0; g.nseg = 2; }
-  g.B = B; g.T_in = Tp_in; g.Tv_in = T; g.T_virt = T_virt; g.Tv_out = Tv_out; g.T_out = Tp_out;
-  g.stride = stride; g.up_mode = up_mode;
-  g.up_scale = up_mode == DV_UP_SIZE ? (float)T / (float)up_T : 1.f;
-  g.Kp = taps * (c0 + c1) + c_sc; g.ldo = Cout;
-  return DV_OK;
-}
-
-extern "C" int dv_op_conv_rows_variant(int32_t B, int32_t T, int32_t Tp_in, int32_t c0, int32_t c1, int32_t c_sc, int32_t Cout, int32_t taps,
-                                       int32_t stride, int32_t up_mode, int32_t up_T, int32_t Tp_out, int32_t tile, int32_t precision,
-                                       int32_t* variant, int32_t* tile_kind, int32_t* nsplit, int32_t* candidates, int32_t cap) {
-  const char* what = "dv_op_conv_rows_variant";
-  if (!variant || !tile_kind || !nsplit || cap < 0 || (cap > 0 && !candidates)) return dv_fail(DV_ERR_INVALID, "%s: null argument", what);
-  GemmParams g;
-  if (int rc = conv_rows_shape(g, B, T, Tp_in, c0, c1, c_sc, Cout, taps, stride, up_mode, up_T, Tp_out, 0, tile, precision, what)) return rc;
-  const int v = gemm_variant(g);
-  const int kind = gemm_variant_tile(g, v);
-  if (v < 0 || kind < 0) return dv_fail(DV_ERR_INVALID, "%s: no instantiation for tile 0x%x", what, tile);
-  *variant = v; *tile_kind = kind; *nsplit = precision == DV_PREC_BF16X3 ? 3 : 1;
-  int cand[16];
-  const int n = gemm_candidates(g, cand, 16);
-  for (int i = 0; i < cap; ++i) candidates[i] = i < n ? cand[i] : 0;   // (0 = DV_GT_AUTO ends the list)
-  return DV_OK;
-}
-
-extern "C" int dv_op_conv_rows(const float* x0, const float* x1, const float* w, const float* bias, const float* x_sc, const float* w_sc,
-                               float* y, uint16_t* y_hi, uint16_t* y_lo, float* stats16, int32_t B, int32_t T, int32_t Tp_in, int32_t c0,
-                               int32_t c1, int32_t c_sc, int32_t Cout, int32_t taps, int32_t stride, int32_t up_mode, int32_t up_T,
-                               int32_t Tp_out, int32_t tile, int32_t precision, void* stream) {
-  const char* what = "dv_op_conv_rows";
-  GemmParams g;
-  if (int rc = conv_rows_shape(g, B, T, Tp_in, c0, c1, c_sc, Cout, taps, stride, up_mode, up_T, Tp_out, stats16 != nullptr, tile, precision, what)) return rc;
-  const bool x3 = precision == DV_PREC_BF16X3;
-  if (!x0 || !w || (!y && !y_hi)) return dv_fail(DV_ERR_INVALID, "%s: x0, w and an output (y and / or y_hi) are required", what);
-  if ((c1 > 0) != (x1 != nullptr)) return dv_fail(DV_ERR_INVALID, "%s: x1 goes with c1 > 0, and only with it", what);
-  if (c_sc > 0 ? (!x_sc || !w_sc) : (x_sc || w_sc)) return dv_fail(DV_ERR_INVALID, "%s: x_sc and w_sc go with c_sc > 0, and only with it", what);
-  if (y_hi && x3 && !y_lo) return dv_fail(DV_ERR_INVALID, "%s: bf16x3 plane output needs y_lo", what);
-  if (!y_hi && y_lo) return dv_fail(DV_ERR_INVALID, "%s: y_lo without y_hi", what);
-  if (!al16(y) || !al16(y_hi) || !al16(y_lo) || !al16(x0) || !al16(x1) || !al16(x_sc) || !al16(stats16))
-    return dv_fail(DV_ERR_INVALID, "%s: the sources and the outputs must be 16-byte aligned", what);
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(gemm_init());
-  gemm_env_refresh();
-  HIPCHK(attn_init());
-  const int Kp = g.Kp, Npad = g.N_pad, cin = c0 + c1;
-  const size_t rows = (size_t)B * Tp_in;
-  OpScratch sc;
-  // every operand plane: [B * Tp_in rows | CONV_ROWS_GUARD rows of bf16 NaN] - a gather that runs past the last utterance shows
-  const int widths[3] = {c0, c1, c_sc};
-  const float* srcs[3] = {x0, x1, x_sc};
-  bf16_t* ph[3] = {nullptr, nullptr, nullptr}; bf16_t* pl[3] = {nullptr, nullptr, nullptr};
-  for (int i = 0; i < 3; ++i) {
-    if (widths[i] == 0) continue;
-    const size_t el = rows * widths[i], gel = (size_t)CONV_ROWS_GUARD * widths[i];
-    ph[i] = sc.get<bf16_t>((el + gel) * 2, st, false);
-    pl[i] = x3 ? sc.get<bf16_t>((el + gel) * 2, st, false) : nullptr;
-    if (!ph[i] || (x3 && !pl[i])) return dv_fail(DV_ERR_HIP, "%s: hipMalloc failed", what);
-    HIPCHK(launch_split(srcs[i], ph[i], pl[i], (int64_t)el, st));
-    HIPCHK(hipMemsetD16Async((hipDeviceptr_t)(ph[i] + el), 0x7fc1, gel, st));
-    if (pl[i]) HIPCHK(hipMemsetD16Async((hipDeviceptr_t)(pl[i] + el), 0x7fc1, gel, st));
-  }
-  bf16_t* hi = sc.get<bf16_t>((size_t)Npad * Kp * 2, st, true);
-  bf16_t* lo = x3 ? sc.get<bf16_t>((size_t)Npad * Kp * 2, st, true) : nullptr;
-  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
-  if (!hi || !zp || (x3 && !lo)) return dv_fail(DV_ERR_HIP, "%s: hipMalloc failed", what);
-  PackSpec s{};
-  s.src = w; s.N = Cout; s.kind = 1; s.C = cin; s.taps = taps; s.c_pad = cin; s.k_off = 0; s.n_off = 0;
-  HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
-  if (c_sc > 0) {
-    s.src = w_sc; s.C = c_sc; s.taps = 1; s.c_pad = c_sc; s.k_off = taps * cin;
-    HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
-  }
-  g.seg[0].a0_hi = ph[0]; g.seg[0].a0_lo = pl[0]; g.seg[0].a1_hi = ph[1]; g.seg[0].a1_lo = pl[1];
-  g.seg[1].a0_hi = ph[2]; g.seg[1].a0_lo = pl[2];
-  g.w_hi = hi; g.w_lo = lo; g.bias = bias; g.zero_page = zp;
-  g.out = y; g.out_hi = reinterpret_cast<bf16_t*>(y_hi); g.out_lo = x3 ? reinterpret_cast<bf16_t*>(y_lo) : nullptr; g.stats16 = stats16;
-  hipError_t e = launch_gemm(g, precision, st);   // (no fragment-major weights: always k_gemm)
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-extern "C" int dv_op_group_stats(const float* x, float* mean, float* rstd, int32_t B, int32_t T, int32_t C, int32_t groups,
-                                 float eps, void* stream) {
-  if (!x || !mean || !rstd || C % groups != 0 || (C / groups) % 4 != 0 || groups > 64)
-    return dv_fail(DV_ERR_INVALID, "dv_op_group_stats: bad argument");
-  hipStream_t st = (hipStream_t)stream;
-  const int nchunk = std::max(1, std::min(64, (T + 63) / 64));
-  double* part = nullptr;
-  HIPCHK(hipMalloc((void**)&part, (size_t)B * nchunk * groups * 2 * sizeof(double)));
-  HIPCHK(launch_gn_partial(x, C, nullptr, 0, part, B, T, groups, nchunk, st));
-  HIPCHK(launch_gn_finalize(part, nchunk, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, mean, rstd, B, T, C, groups, eps, st));
-  HIPCHK(hipStreamSynchronize(st));
-  (void)hipFree(part);
-  return DV_OK;
-}
-
-extern "C" int dv_op_attention_prec(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
-                                    int32_t H, int32_t Tq, int32_t Tk, int32_t d, int32_t precision, void* stream) {
-  if (!q || !k || !v || !o) return dv_fail(DV_ERR_INVALID, "dv_op_attention: null argument");
-  if (precision != DV_PREC_BF16X3 && precision != DV_PREC_BF16) return dv_fail(DV_ERR_INVALID, "dv_op_attention: precision %d is not a DV_PREC_*", precision);
-  if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return dv_fail(DV_ERR_INVALID, "dv_op_attention: B, H, Tq and Tk must be positive");
-  AttnParams a{};
-  a.q = q; a.k = k; a.v = v; a.bias = bias; a.o = o; a.o_hi = nullptr; a.o_lo = nullptr;
-  a.ldq = a.ldk = a.ldv = a.ldo = H * d;
-  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.d = d; a.scale = 1.0f / sqrtf((float)d); a.nsplit = precision == DV_PREC_BF16X3 ? 3 : 1;
-  HIPCHK(attn_init());
-  hipError_t e = launch_attention(a, (hipStream_t)stream);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "attention launch failed: %s (d must be a multiple of 4, <= 64)", hipGetErrorString(e));
-  return DV_OK;
-}
-
-extern "C" int dv_op_attention(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
-                               int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream) {
-  return dv_op_attention_prec(q, k, v, bias, o, B, H, Tq, Tk, d, DV_PREC_BF16X3, stream);
-}
-
-// k_attention_frag as the forward runs its cross attention: K | V -> split fragments in the hoisted layout (launch_kv_frag), the
-// key bias as log2-domain rows of whole 32-key tiles (launch_xbias), then launch_attention_frag's own choice of instantiation
-extern "C" int dv_op_attention_frag(const float* q, const float* k, const float* v, const float* bias, float* o, int32_t B,
-                                    int32_t H, int32_t Tq, int32_t Tk, int32_t d, void* stream) {
-  if (!q || !k || !v || !o || B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return dv_fail(DV_ERR_INVALID, "dv_op_attention_frag: bad argument");
-  if (d <= 0 || d % 16 != 0 || d > 64) return dv_fail(DV_ERR_INVALID, "dv_op_attention_frag: d = %d must be a multiple of 16, <= 64", d);
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(attn_init());
-  const int C = H * d, nT = (Tk + 31) / 32, KSq = d / 16, NBv = (d + 31) / 32;
-  const size_t kel = (size_t)B * H * nT * KSq * 64 * 8, vel = (size_t)B * H * nT * 2 * NBv * 64 * 8;
-  OpScratch sc;
-  float* kv = sc.get<float>((size_t)B * Tk * 2 * C * 4, st, false);
-  bf16_t* kf_hi = sc.get<bf16_t>(kel * 2, st, false); bf16_t* kf_lo = sc.get<bf16_t>(kel * 2, st, false);
-  bf16_t* vf_hi = sc.get<bf16_t>(vel * 2, st, false); bf16_t* vf_lo = sc.get<bf16_t>(vel * 2, st, false);
-  float* xb = sc.get<float>((size_t)B * nT * 32 * 4, st, false);
-  if (!kv || !kf_hi || !kf_lo || !vf_hi || !vf_lo || !xb) return dv_fail(DV_ERR_HIP, "dv_op_attention_frag: hipMalloc failed");
-  HIPCHK(hipMemcpy2DAsync(kv, (size_t)2 * C * 4, k, (size_t)C * 4, (size_t)C * 4, (size_t)B * Tk, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpy2DAsync(kv + C, (size_t)2 * C * 4, v, (size_t)C * 4, (size_t)C * 4, (size_t)B * Tk, hipMemcpyDeviceToDevice, st));
-  HIPCHK(launch_kv_frag(kv, kf_hi, kf_lo, vf_hi, vf_lo, B, Tk, C, H, st));
-  HIPCHK(launch_xbias(bias, xb, B, Tk, nT, st));
-  AttnFragParams a{};
-  a.q = q; a.ldq = C;
-  a.kf_hi = kf_hi; a.kf_lo = kf_lo; a.vf_hi = vf_hi; a.vf_lo = vf_lo;
-  a.k_b = H * nT * KSq; a.k_h = nT * KSq; a.k_t = KSq;
-  a.v_b = H * nT * 2 * NBv; a.v_h = nT * 2 * NBv; a.v_t = 2 * NBv; a.v_kb = NBv; a.v_nb = 1; a.self_layout = 0;
-  a.bias = xb; a.bias_ld = nT * 32;
-  a.o = o; a.o_hi = nullptr; a.o_lo = nullptr; a.ldo = C;
-  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.d = d; a.scale = 1.0f / sqrtf((float)d); a.nsplit = 3;
-  hipError_t e = launch_attention_frag(a, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_attention_frag: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-// The k = 3 convolutions of ResnetBlock2D / Upsample2D as the forward launches them: split planes of a channels-last input in a
-// (padded) row space, packed weights AND their fragment-major copies, through launch_gemm - which then routes to k_conv3 /
-// k_conv3s / k_conv3u.  A shape launch_gemm would hand to k_gemm is refused.
-extern "C" int dv_op_conv3(const float* x, const float* w, const float* bias, const float* x_sc, const float* w_sc, float* y, int32_t B,
-                           int32_t Cin, int32_t T, int32_t Tp, int32_t Cout, int32_t Csc, int32_t up2, void* stream) {
-  if (!x || !w || !y || B <= 0 || Cin <= 0 || T <= 0 || Tp < T || Cout <= 0 || Csc < 0 || (Csc > 0 && (!x_sc || !w_sc || up2)))
-    return dv_fail(DV_ERR_INVALID, "dv_op_conv3: bad argument");
-  if (Cin % 64 != 0 || Csc % 64 != 0 || 2 * (size_t)std::max(Cin, Csc) + 256 > DV_ZERO_PAGE_BYTES)
-    return dv_fail(DV_ERR_INVALID, "dv_op_conv3: Cin = %d / Csc = %d must be multiples of 64 within one source tensor's width", Cin, Csc);
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(gemm_init());
-  gemm_env_refresh();
-  HIPCHK(attn_init());
-  const int Kp = 3 * Cin + Csc, Npad = rup(Cout, 128);
-  const int Tv_out = up2 ? 2 * T : T, T_out = up2 ? rup(2 * T, 32) : Tp;
-  GemmParams g{};
-  g.nseg = Csc > 0 ? 2 : 1; g.B = B;
-  g.T_in = Tp; g.Tv_in = T; g.T_out = T_out; g.Tv_out = g.T_virt = Tv_out;
-  g.stride = 1; g.up_mode = up2 ? UP_X2 : UP_NONE;
-  g.M = B * T_out; g.N = Cout; g.epi = EPI_STORE; g.ldo = Cout; g.ldres = Cout; g.Kp = Kp; g.N_pad = Npad; g.bias = bias;
-  g.seg[0].c0 = Cin; g.seg[0].taps = 3; g.seg[0].pad = 1;
-  if (Csc > 0) { g.seg[1].c0 = Csc; g.seg[1].taps = 1; g.seg[1].pad = 0; }
-  const int route = gemm_conv3_up_ok(g) ? 2 : ((gemm_conv3_shape_ok(g) && Kp == gemm_conv3_k(g)) ? 1 : 0);
-  if (route == 0)
-    return dv_fail(DV_ERR_INVALID, "dv_op_conv3: B=%d Cin=%d T=%d Tp=%d Cout=%d Csc=%d up2=%d is not a shape of the convolution kernels "
-                   "(it would run on k_gemm)", B, Cin, T, Tp, Cout, Csc, up2);
-  OpScratch sc;
-  const size_t xe = (size_t)B * Tp * Cin, se = (size_t)B * Tp * Csc, we = (size_t)Npad * Kp;
-  bf16_t* xh = sc.get<bf16_t>(xe * 2, st, false); bf16_t* xl = sc.get<bf16_t>(xe * 2, st, false);
-  bf16_t* sh = Csc > 0 ? sc.get<bf16_t>(se * 2, st, false) : nullptr; bf16_t* sl = Csc > 0 ? sc.get<bf16_t>(se * 2, st, false) : nullptr;
-  bf16_t* hi = sc.get<bf16_t>(we * 2, st, true); bf16_t* lo = sc.get<bf16_t>(we * 2, st, true);
-  bf16_t* fhi = sc.get<bf16_t>(we * 2, st, false); bf16_t* flo = sc.get<bf16_t>(we * 2, st, false);
-  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
-  if (!xh || !xl || !hi || !lo || !fhi || !flo || !zp || (Csc > 0 && (!sh || !sl))) return dv_fail(DV_ERR_HIP, "dv_op_conv3: hipMalloc failed");
-  HIPCHK(launch_split(x, xh, xl, (int64_t)xe, st));
-  if (Csc > 0) HIPCHK(launch_split(x_sc, sh, sl, (int64_t)se, st));
-  PackSpec s{};
-  s.src = w; s.N = Cout; s.kind = 1; s.C = Cin; s.taps = 3; s.c_pad = Cin; s.k_off = 0; s.n_off = 0;
-  HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
-  if (Csc > 0) {
-    s.src = w_sc; s.C = Csc; s.taps = 1; s.c_pad = Csc; s.k_off = 3 * Cin;
-    HIPCHK(launch_pack_weight(s, hi, lo, Kp, st));
-  }
-  HIPCHK(launch_relayout_frag(hi, fhi, Npad, Kp, st));
-  HIPCHK(launch_relayout_frag(lo, flo, Npad, Kp, st));
-  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl;
-  if (Csc > 0) { g.seg[1].a0_hi = sh; g.seg[1].a0_lo = sl; }
-  g.w_hi = hi; g.w_lo = lo; g.wf_hi = fhi; g.wf_lo = flo; g.out = y; g.zero_page = zp;
-  if (route == 1) {   // the 128-frame level's long-K convolutions run as a fused split-K pair on the streaming kernel: here too
-    int dev = 0, n_cu = 0;
-    (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (gemm_conv3_split(g, n_cu) == 2 && ((g.M + 31) / 32) * ((g.N + 31) / 32) <= 4096) {
-      g.sk_split = 2;
-      g.sk_buf = sc.get<float>(gemm_conv3_split_bytes(g), st, false);
-      g.sk_ticket = sc.get<unsigned>(4096 * sizeof(unsigned), st, true);
-      if (!g.sk_buf || !g.sk_ticket) return dv_fail(DV_ERR_HIP, "dv_op_conv3: hipMalloc failed");
-    }
-  }
-  hipError_t e = launch_gemm(g, DV_PREC_BF16X3, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_conv3: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-// ----------------------------------------------------------------------------- normalisation entry points
-// The LayerNorm / GroupNorm routes of the forward through the launchers the engine calls (include/dvits_hip.h).
-
-extern "C" int dv_op_layer_norm(const float* x, const float* gamma, const float* beta, const float* rowmask, float* y, uint16_t* y_hi,
-                                uint16_t* y_lo, float* mean, float* rstd, int32_t M, int32_t C, float eps, int32_t route, void* stream) {
-  if (!x || M <= 0 || C <= 0 || !(eps >= 0.f) || !std::isfinite(eps)) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: bad argument");
-  if (C % 4 != 0 || C > 2048) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: C = %d must be a multiple of 4, <= 2048", C);
-  if (!al16(x) || !al16(gamma) || !al16(beta) || !al16(y) || !al16(y_hi) || !al16(y_lo))
-    return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: x, gamma, beta and the outputs must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  switch (route) {
-    case DV_LN_STATS:
-      if (!mean || !rstd || y || y_hi || y_lo || rowmask) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_STATS writes mean and rstd only");
-      e = launch_ln_stats(x, mean, rstd, M, C, eps, st);
-      break;
-    case DV_LN_ROWS:
-      if (!gamma || !beta || !y || y_hi || y_lo || mean || rstd || rowmask) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_ROWS needs gamma, beta and y only");
-      e = launch_layernorm_rows(x, gamma, beta, y, M, C, eps, st);
-      break;
-    case DV_LN_APPLY:
-      if (!y_hi || y || gamma || beta || mean || rstd || rowmask) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_APPLY writes planes only, without affine");
-      e = launch_ln_apply(x, y_hi, y_lo, M, C, eps, st);
-      break;
-    case DV_LN_AFFINE:
-      if (!gamma || !beta || (!y && !y_hi) || (y_lo && !y_hi) || mean || rstd) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: DV_LN_AFFINE needs gamma, beta and y and / or planes");
-      e = launch_ln_affine(x, gamma, beta, rowmask, y, y_hi, y_lo, M, C, eps, st);
-      break;
-    default:
-      return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm: route %d is not one of DV_LN_*", route);
-  }
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_layer_norm: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-extern "C" int dv_op_layer_norm_into(const float* x, const float* gamma, const float* beta, float* y, int32_t M, int32_t C, float eps,
-                                     int32_t rows_per_batch, int32_t out_rows_per_batch, int32_t out_row_off, void* stream) {
-  if (!x || !gamma || !beta || !y || M <= 0 || C <= 0 || !(eps >= 0.f) || !std::isfinite(eps)) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: bad argument");
-  if (C % 4 != 0 || C > 2048) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: C = %d must be a multiple of 4, <= 2048", C);
-  if (rows_per_batch <= 0 || M % rows_per_batch != 0 || out_row_off < 0 || out_row_off > out_rows_per_batch - rows_per_batch)
-    return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: %d rows per utterance do not fit slots of %d rows at offset %d (M = %d)", rows_per_batch,
-                   out_rows_per_batch, out_row_off, M);
-  if (!al16(x) || !al16(gamma) || !al16(beta) || !al16(y)) return dv_fail(DV_ERR_INVALID, "dv_op_layer_norm_into: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = launch_layernorm_rows_into(x, gamma, beta, y, M, C, eps, rows_per_batch, out_rows_per_batch, out_row_off, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_layer_norm_into: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-extern "C" int dv_op_prompt_pre(const float* prompt, const float* keep, const float* gamma, const float* beta, uint16_t* hi, uint16_t* lo,
-                                float* key_bias, int32_t B, int32_t C, int32_t L, int32_t cpad, float eps, void* stream) {
-  if (!prompt || !keep || !gamma || !beta || !hi || !key_bias || B <= 0 || L <= 0 || !(eps >= 0.f) || !std::isfinite(eps))
-    return dv_fail(DV_ERR_INVALID, "dv_op_prompt_pre: bad argument");
-  if (C < 1 || C > 512 || cpad < C || cpad > 512) return dv_fail(DV_ERR_INVALID, "dv_op_prompt_pre: 1 <= C = %d <= cpad = %d <= 512 is required", C, cpad);
-  if ((int64_t)B * L > INT32_MAX / 512) return dv_fail(DV_ERR_INVALID, "dv_op_prompt_pre: B * L = %lld exceeds %d", (long long)B * L, INT32_MAX / 512);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = launch_prompt_pre(prompt, keep, gamma, beta, hi, lo, key_bias, B, C, L, cpad, eps, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_prompt_pre: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-// ----------------------------------------------------------------------------- conditioning entry points
-// The fp32 kernels of the conditioning path (kernels_misc.hip) through the launchers the cond and step schedules call.
-
-extern "C" int dv_op_timestep_embedding(const float* t, float* out, int32_t B, int32_t dim, void* stream) {
-  if (!t || !out) return dv_fail(DV_ERR_INVALID, "dv_op_timestep_embedding: null pointer");
-  if (B < 1 || dim < 2 || dim % 2 != 0 || (int64_t)B * (dim / 2) > INT32_MAX - 256)
-    return dv_fail(DV_ERR_INVALID, "dv_op_timestep_embedding: B = %d >= 1 rows of an even dim = %d >= 2, B * dim / 2 < 2^31 - 256, are required", B, dim);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = launch_timestep_sincos(t, out, B, dim, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_timestep_embedding: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-extern "C" int dv_op_small_linear(const float* in, int32_t ldin, const float* w, const float* bias, const float* add, float* out, int32_t ldo,
-                                  int32_t M, int32_t K, int32_t N, int32_t silu_in, int32_t silu_out, int32_t route, int32_t add_rows,
-                                  void* stream) {
-  if (!in || !w || !out) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: null pointer");
-  if (route != 0 && route != 1) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: route %d is neither 0 (k_small_linear) nor 1 (k_small_linear_t)", route);
-  if ((silu_in != 0 && silu_in != 1) || (silu_out != 0 && silu_out != 1)) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: silu_in and silu_out are 0 or 1");
-  if (M < 1 || M > 65536 || K < 1 || K > 16384 || N < 1 || N > (1 << 20))
-    return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: 1 <= M = %d <= 65536, 1 <= K = %d <= 16384, 1 <= N = %d <= 2^20 are required", M, K, N);
-  if (ldin < K || ldo < N) return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: ldin = %d >= K = %d and ldo = %d >= N = %d are required", ldin, K, ldo, N);
-  if (add_rows < 0 || (add_rows > 0 && (route != 1 || !add)))
-    return dv_fail(DV_ERR_INVALID, "dv_op_small_linear: add_rows = %d needs route 1 and an add tensor", add_rows);
-  hipStream_t st = (hipStream_t)stream;
-  const hipError_t e = route == 0 ? launch_small_linear(in, ldin, w, bias, add, out, ldo, M, K, N, silu_in, silu_out, st)
-                                  : launch_small_linear_t(in, ldin, w, bias, add, out, ldo, M, K, N, silu_in, silu_out, st, add_rows);
-  if (e == hipErrorInvalidValue)   // the launchers' own refusals: nothing was launched
-    return route == 0 ? dv_fail(DV_ERR_INVALID, "dv_op_small_linear: M x K = %d x %d floats exceed the 64 KiB of LDS k_small_linear stages its rows in", M, K)
-                      : dv_fail(DV_ERR_INVALID, "dv_op_small_linear: K = %d exceeds the 512 input columns k_small_linear_t's 64 KiB of LDS hold", K);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_small_linear: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-extern "C" int dv_op_pool_attention(float* seq, const float* pos, const float* q, const float* kv, float* out, int32_t B, int32_t L, int32_t D,
-                                    int32_t heads, int32_t stage, void* stream) {
-  if (stage != 0 && stage != 1) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: stage %d is neither 0 (k_mean_token) nor 1 (k_pool_attn)", stage);
-  if (B < 1 || B > 65535 || L < 1 || L > (1 << 20) || D < 1 || D > 8192)
-    return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: 1 <= B = %d <= 65535, 1 <= L = %d <= 2^20, 1 <= D = %d <= 8192 are required", B, L, D);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  if (stage == 0) {
-    if (!seq || !pos || q || kv || out) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: stage 0 takes seq and pos only");
-    e = launch_mean_token(seq, pos, B, L, D, st);
-  } else {
-    if (!q || !kv || !out || seq || pos) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: stage 1 takes q, kv and out only");
-    if (heads < 1 || heads > 65535 || D % heads != 0) return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: D = %d is not a multiple of heads = %d >= 1", D, heads);
-    e = launch_pool_attn(q, kv, out, B, L + 1, D, heads, st);
-    if (e == hipErrorInvalidValue)   // the launcher's own refusal: nothing was launched
-      return dv_fail(DV_ERR_INVALID, "dv_op_pool_attention: D / heads = %d exceeds the 8 channels per head k_pool_attn accumulates", D / heads);
-  }
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_pool_attention: launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-// Producer GEMM (+ residual) with the raw planes and the row partials of ln_produce, then the consumer GEMM as ln_consume sets it
-// up: gamma folded into the packed weights, u and the beta-folded bias by the packing launchers Builder::pack runs.
-extern "C" int dv_op_linear_ln(const float* x, const float* w1, const float* b1, const float* res, const float* gamma, const float* beta,
-                               const float* w2, const float* b2, int32_t M, int32_t K, int32_t C, int32_t N, int32_t fused, float* y1,
-                               float* rowstat, float* y2, void* stream) {
-  if (!x || !w1 || !gamma || !beta || !w2 || !y1 || !y2 || M <= 0 || N <= 0 || (fused != 0 && fused != 1) || (fused && !rowstat))
-    return dv_fail(DV_ERR_INVALID, "dv_op_linear_ln: bad argument");
-  if (K <= 0 || K % 32 != 0 || 2 * (size_t)K + 256 > DV_ZERO_PAGE_BYTES) return dv_fail(DV_ERR_INVALID, "dv_op_linear_ln: K = %d must be a multiple of 32 within one source tensor's width", K);
-  if (C <= 0 || C % 32 != 0 || C > 512) return dv_fail(DV_ERR_INVALID, "dv_op_linear_ln: C = %d must be a multiple of 32, <= 512 (the consumer holds 16 partials per row)", C);
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(gemm_init());
-  gemm_env_refresh();
-  HIPCHK(attn_init());
-  const int Cpad = rup(C, 128), Npad = rup(N, 128);
-  OpScratch sc;
-  bf16_t* xh = sc.get<bf16_t>((size_t)M * K * 2, st, false); bf16_t* xl = sc.get<bf16_t>((size_t)M * K * 2, st, false);
-  bf16_t* w1h = sc.get<bf16_t>((size_t)Cpad * K * 2, st, true); bf16_t* w1l = sc.get<bf16_t>((size_t)Cpad * K * 2, st, true);
-  bf16_t* w2h = sc.get<bf16_t>((size_t)Npad * C * 2, st, true); bf16_t* w2l = sc.get<bf16_t>((size_t)Npad * C * 2, st, true);
-  bf16_t* ph = sc.get<bf16_t>((size_t)M * C * 2, st, false); bf16_t* pl = sc.get<bf16_t>((size_t)M * C * 2, st, false);
-  float* u = sc.get<float>((size_t)Npad * 4, st, true); float* pb = sc.get<float>((size_t)Npad * 4, st, true);
-  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
-  if (!xh || !xl || !w1h || !w1l || !w2h || !w2l || !ph || !pl || !u || !pb || !zp) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: hipMalloc failed");
-  HIPCHK(launch_split(x, xh, xl, (int64_t)M * K, st));
-  PackSpec s{};
-  s.src = w1; s.N = C; s.kind = 0; s.C = K; s.taps = 1; s.c_pad = K;
-  HIPCHK(launch_pack_weight(s, w1h, w1l, K, st));
-  s.src = w2; s.N = N; s.C = C; s.c_pad = C; s.kscale = gamma;   // (both routes: k_ln_apply has no affine either)
-  HIPCHK(launch_pack_weight(s, w2h, w2l, C, st));
-  HIPCHK(launch_fold_bias(w2, nullptr, gamma, u, N, C, 0, 0, st));
-  HIPCHK(launch_fold_bias(w2, b2, beta, pb, N, C, 0, 0, st));
-  GemmParams g{};
-  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl; g.seg[0].c0 = K; g.seg[0].taps = 1;
-  g.nseg = 1; g.B = 1; g.T_in = g.T_out = g.T_virt = M; g.stride = 1;
-  g.w_hi = w1h; g.w_lo = w1l; g.Kp = K; g.N_pad = Cpad; g.bias = b1;
-  g.M = M; g.N = C; g.epi = res ? EPI_RESIDUAL : EPI_STORE; g.res = res; g.ldres = C; g.out = y1; g.ldo = C; g.zero_page = zp;
-  if (fused) { g.out_hi = ph; g.out_lo = pl; g.rowstat_out = rowstat; }
-  hipError_t e = launch_gemm(g, DV_PREC_BF16X3, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: producer launch failed: %s", hipGetErrorString(e));
-  if (!fused) {
-    e = launch_ln_apply(y1, ph, pl, M, C, 1e-5f, st);
-    if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: k_ln_apply launch failed: %s", hipGetErrorString(e));
-  }
-  GemmParams c{};
-  c.seg[0].a0_hi = ph; c.seg[0].a0_lo = pl; c.seg[0].c0 = C; c.seg[0].taps = 1;
-  c.nseg = 1; c.B = 1; c.T_in = c.T_out = c.T_virt = M; c.stride = 1;
-  c.w_hi = w2h; c.w_lo = w2l; c.Kp = C; c.N_pad = Npad; c.bias = pb;
-  c.M = M; c.N = N; c.epi = EPI_STORE; c.out = y2; c.ldo = N; c.zero_page = zp;
-  if (fused) { c.ln_stat = rowstat; c.ln_nblk = C / 32; c.ln_u = u; c.ln_eps = 1e-5f; }
-  e = launch_gemm(c, DV_PREC_BF16X3, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_ln: consumer launch failed: %s", hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}
-
-extern "C" int dv_op_linear_gn(const float* x, const float* w, const float* b, const float* gamma, const float* beta, int32_t B, int32_t T,
-                               int32_t Tp, int32_t K, int32_t C, int32_t G, float eps, int32_t route, float* y, float* stats,
-                               uint16_t* y_norm_hi, uint16_t* y_norm_lo, void* stream) {
-  if (!x || !w || !gamma || !beta || !y || !y_norm_hi || !y_norm_lo || B <= 0 || T <= 0 || C <= 0 || G <= 0 || !(eps >= 0.f) || !std::isfinite(eps))
-    return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: bad argument");
-  if (route != DV_GN_STAT16 && route != DV_GN_SLAB && route != DV_GN_KSTAT16) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: route %d is not one of DV_GN_*", route);
-  if (K <= 0 || K % 32 != 0 || 2 * (size_t)K + 256 > DV_ZERO_PAGE_BYTES) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: K = %d must be a multiple of 32 within one source tensor's width", K);
-  if (Tp % 32 != 0 || T > Tp || T <= Tp - 32) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: Tp = %d must be a multiple of 32 with Tp - 32 < T = %d <= Tp", Tp, T);
-  if ((int64_t)B * Tp > INT32_MAX / 2048) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: B * Tp = %lld rows are too many", (long long)B * Tp);
-  if (C % G != 0 || G > 64 || C / G > 512) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: C = %d, G = %d: at most 64 groups of at most 512 channels", C, G);
-  if (route == DV_GN_SLAB ? (C / G) % 4 != 0 : (C / G) % 16 != 0)
-    return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: %d channels per group: block statistics need whole 16-channel blocks, the column slab multiples of 4", C / G);
-  // the column slab's consumer and the standalone k_stat16 have no padded-row form (launch_gn_apply, launch_stat16)
-  if (route != DV_GN_STAT16 && T != Tp) return dv_fail(DV_ERR_INVALID, "dv_op_linear_gn: this route has no padded-row form: T = %d must equal Tp = %d", T, Tp);
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(gemm_init());
-  gemm_env_refresh();
-  HIPCHK(attn_init());
-  const int M = B * Tp, Npad = rup(C, 128);
-  const size_t nstat = route == DV_GN_SLAB ? (size_t)(M / 32) * C * 2 : (size_t)(M / 32) * (C / 16) * 2;
-  OpScratch sc;
-  bf16_t* xh = sc.get<bf16_t>((size_t)M * K * 2, st, false); bf16_t* xl = sc.get<bf16_t>((size_t)M * K * 2, st, false);
-  bf16_t* wh = sc.get<bf16_t>((size_t)Npad * K * 2, st, true); bf16_t* wl = sc.get<bf16_t>((size_t)Npad * K * 2, st, true);
-  bf16_t* zp = sc.get<bf16_t>(DV_ZERO_PAGE_BYTES, st, true);
-  float* sbuf = stats ? stats : sc.get<float>(nstat * 4, st, false);
-  if (!xh || !xl || !wh || !wl || !zp || !sbuf) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: hipMalloc failed");
-  HIPCHK(launch_split(x, xh, xl, (int64_t)M * K, st));
-  PackSpec s{};
-  s.src = w; s.N = C; s.kind = 0; s.C = K; s.taps = 1; s.c_pad = K;
-  HIPCHK(launch_pack_weight(s, wh, wl, K, st));
-  GemmParams g{};
-  g.seg[0].a0_hi = xh; g.seg[0].a0_lo = xl; g.seg[0].c0 = K; g.seg[0].taps = 1;
-  g.nseg = 1; g.B = B; g.T_in = g.T_out = Tp; g.Tv_in = g.Tv_out = g.T_virt = T; g.stride = 1;
-  g.w_hi = wh; g.w_lo = wl; g.Kp = K; g.N_pad = Npad; g.bias = b;
-  g.M = M; g.N = C; g.epi = EPI_STORE; g.out = y; g.ldo = C; g.zero_page = zp;
-  if (route == DV_GN_STAT16) g.stats16 = sbuf;
-  if (route == DV_GN_SLAB) g.stats = sbuf;
-  hipError_t e = launch_gemm(g, DV_PREC_BF16X3, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: launch failed: %s", hipGetErrorString(e));
-  if (route == DV_GN_KSTAT16) {
-    e = launch_stat16(y, sbuf, M, C, st);
-    if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: k_stat16 launch failed: %s", hipGetErrorString(e));
-  }
-  GnApplyParams gp{};
-  gp.a0 = y; gp.c0 = C;
-  if (route == DV_GN_SLAB) gp.slab0 = sbuf; else gp.st16_0 = sbuf;
-  gp.gamma = gamma; gp.beta = beta; gp.eps = eps; gp.groups = G;
-  gp.out_hi = y_norm_hi; gp.out_lo = y_norm_lo; gp.B = B; gp.T = Tp; gp.Tv = T;
-  e = launch_gn_apply(gp, st);
-  if (e != hipSuccess) return dv_fail(DV_ERR_HIP, "dv_op_linear_gn: k_gn_apply refused C = %d, G = %d, T = %d, Tp = %d on this route: %s", C, G, T, Tp, hipGetErrorString(e));
-  HIPCHK(hipStreamSynchronize(st));
-  return DV_OK;
-}

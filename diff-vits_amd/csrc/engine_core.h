@@ -1,5 +1,6 @@
-// Host-side core shared by the engines behind the C ABI (engine.hip, tenc.hip, qenc.hip): error plumbing, the raw-weight
-// store, the plan-time allocator, the launch list and the pieces every planner over channels-last rows m = b * T + t needs.
+// Host-side core shared by the engines behind the C ABI (engine.hip, tenc.hip, qenc.hip, voc.hip) and the single-operator entry
+// points (ops.hip): error plumbing, the raw-weight store, the plan-time allocator, the launch list and the pieces every planner
+// over channels-last rows m = b * T + t needs.
 // Host code only: no kernel lives here.
 #pragma once
 #include "../../include/dvits_hip.h"
@@ -80,7 +81,7 @@ struct WeightStore {
 // ----------------------------------------------------------------------------- plan-time device memory
 // DVITS_POISON (development; read at every fill, so at every prepare: tests flip it inside one process): memory that a plan
 // allocates WITHOUT defining its contents - the denoiser's and the prompt encoder's slab, every dmalloc(zero = false), every
-// OpScratch::get(zero = false) - is filled once, on the plan's stream, before the first operation that could write it:
+// OpScratch::get(UNWRITTEN) of ops.hip - is filled once, on the plan's stream, before the first operation that could write it:
 //   nan   byte 0xFF: every fp32 word and every bf16 half is a NaN
 //   big   byte 0x4B: ~1.3e7 as fp32 and as bf16 - finite, so a multiply by a zero mask hides it where it would expose a NaN
 // Unset, "0" or anything else: no fill, nothing counted.  Only floating-point payload lives in such memory (indices, counts,
